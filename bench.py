@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark: ECDSA-P256 signature verifies/s on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--n SIGS_PER_RANK]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--n SIGS_PER_RANK] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
 
 Workload (BASELINE.json configs[3]): 1,048,576
@@ -18,11 +18,19 @@ each verifying its own shard -- no collective on the data path; torch.distribute
 (gloo, CPU) is used only for the barrier and the max-over-ranks time, so torch
 never touches the GPU (it bundles its own HIP runtime).
 
-Also reported on rank 0: p50 quorum-certificate verify latency (host submit ->
-bitmap on host, configs[1]/[2] certificate sizes), the roofline of the
-dominant kernel (HIP-event kernel durations from the timed region), and the
-CPU baseline (oracle port, multi-threaded, bounded sample) beside an OpenSSL
-stand-in.
+A plain run sets up (batch, key registration), warms up, times the K steps
+and prints the result line.  --dump-outputs DIR also writes what the last timed
+step computed: the accept bit of every signature of the rank's batch, as float32
+0/1, in batch order.  The hashes, keys, key indices and the corrupted 1 % are
+seeded; the signatures' nonces are OpenSSL's own (tools/synth.py), so the
+signature bytes differ run to run while the expected bits do not.
+
+With --full, also reported on rank 0: the same steps on one stream, p50
+quorum-certificate verify latency (host submit -> bitmap on host,
+configs[1]/[2] certificate sizes), the roofline of the dominant kernel
+(HIP-event kernel durations from a pass of their own), the host-buffer path,
+the other BASELINE configs, and the CPU baseline (oracle port, multi-threaded,
+bounded sample) beside an OpenSSL stand-in.
 """
 from __future__ import annotations
 
@@ -1118,7 +1126,15 @@ def main():
                     help="consecutive batches alternate over this many library streams (pbftv_stream_create: each "
                          "owns its verify scratch), so batch j+1's scalar stage overlaps batch j's comb; 0 = the "
                          "context's own stream")
-    ap.add_argument("--no-extras", action="store_true", help="skip QC latency, host path, CPU baselines, other configs")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure everything else: the one-stream pass, per-kernel times "
+                         "and roofline, host path, QC latency, single calls, CPU baselines, the other configs")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed (the accept bit of every signature of this rank's "
+                         "batch, float32) to DIR/accept.npy (DIR/accept_rank<R>.npy with several ranks)")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: only the per-kernel times / roofline (no one-stream pass, QC latency, host "
+                         "path, CPU baselines, other configs)")
     ap.add_argument("--no-in-context", action="store_true",
                     help="N > 1: skip the one-process leg over one N-device context (in_context)")
     ap.add_argument("--sha-only", action="store_true", help="only configs[4] (SHA-256 digest kernel), one JSON line")
@@ -1255,10 +1271,17 @@ def main():
     sync_all()
     d.barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        # the bitmap the last step wrote, one value per signature
+        last = dbs[(turn[0] - 1) % len(streams)]
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "accept.npy" if ws == 1 else f"accept_rank{rank}.npy"),
+                np.unpackbits(last.to_host(), bitorder="little")[:n].astype(np.float32))
+    extras = args.full and not args.no_extras
     # the same K steps queued on the context stream only (no overlap between
     # consecutive batches), reported beside the headline
     one_stream_ms = None
-    if args.streams and not args.no_extras:
+    if args.streams and extras:
         d.barrier()
         sync_all()
         t1 = time.perf_counter()
@@ -1272,15 +1295,16 @@ def main():
     # recorded by the library around each scalar / comb launch on its stream
     # (on ONE stream, so no kernel's event window includes another batch's
     # overlapping work: these are the kernels' own durations)
-    ver.set_kernel_timing(True)
-    ver.reset_kernel_times()
-    for _ in range(args.steps):
-        if n:
-            ver.verify_batch_dev(0, dh.ptr, ds.ptr, dk.ptr, n, dbs[0].ptr, stream=streams[0])
-    sync_all()
-    comb_ms, comb_cnt = ver.kernel_time_ms(0, K_ECDSA_COMB)
-    scal_ms, scal_cnt = ver.kernel_time_ms(0, K_ECDSA_SCALARS)
-    ver.set_kernel_timing(False)
+    if args.full:
+        ver.set_kernel_timing(True)
+        ver.reset_kernel_times()
+        for _ in range(args.steps):
+            if n:
+                ver.verify_batch_dev(0, dh.ptr, ds.ptr, dk.ptr, n, dbs[0].ptr, stream=streams[0])
+        sync_all()
+        comb_ms, comb_cnt = ver.kernel_time_ms(0, K_ECDSA_COMB)
+        scal_ms, scal_cnt = ver.kernel_time_ms(0, K_ECDSA_SCALARS)
+        ver.set_kernel_timing(False)
     check = check and all(bool((np.unpackbits(b.to_host(), bitorder="little")[:n].astype(bool) == ok).all())
                           for b in dbs)
     t_max = d.max(elapsed)
@@ -1306,12 +1330,12 @@ def main():
     if one_stream_ms is not None:
         out["ms_per_step_one_stream"] = one_stream_ms
     out["affinity"] = affinity
-    if rank == 0:
+    gb, qb, tb = ver.table_config()
+    if rank == 0 and args.full:
         comb_avg = comb_ms / max(comb_cnt, 1) * 1e-3
         scal_avg = scal_ms / max(scal_cnt, 1) * 1e-3
         kb = scalar_batch(n)
         ms = macs_scalars(kb)
-        gb, qb, tb = ver.table_config()
         mc = macs_comb(gb, qb)
         kern = {
             "ecdsa_comb": {"avg_ms": comb_avg * 1e3, "macs_per_verify": mc, "window_bits": [gb, qb],
@@ -1342,12 +1366,13 @@ def main():
                                                 GATHER_ONLY_TBPS,
                                                 "source": "tools/gather_comb.hip, profiles/r03_gather_comb.txt"}
         out["kernels"] = kern
+    if rank == 0:
         out["config"]["comb_window_bits"] = {"G": gb, "keys": qb, "table_bytes_per_gpu": tb}
         out["registration_s"] = {"keys": args.keys, "wall_s": t_reg, "phases_ms": reg_phases,
                                  "what": "pbftv_register_keys: G table + the key tables built on the device (incl. "
                                          "allocation); phases_ms from the library's PBFTV_TRACE (the table scratch / "
                                          "table kernels lines are the parts of each build)"}
-        if not args.no_extras and ws == 1:
+        if extras and ws == 1:
             # host-buffer path with no armed latency kernel on the GPU (none armed yet)
             out["host_path"] = host_path(ver, H, S, K, ok)
             out["host_path_verifies_per_s"] = out["host_path"]["pageable"]["verifies_per_s"]

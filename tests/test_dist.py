@@ -4,7 +4,8 @@ pbftv_api.cpp uses across a context's devices), verifies it with the CPU
 oracle standing in for its GPU, and the gathered shard bitmaps must equal the
 single-process result.  Also checks bench.py's barrier / max-over-ranks
 reduction.  No collective is on the data path of the product: the gather here
-is only the test's check."""
+is only the test's check.  One GPU test: a plain bench.py run and its
+--dump-outputs."""
 from __future__ import annotations
 
 import os
@@ -147,6 +148,35 @@ def test_bench_gpus_mismatch_fails_loudly():
     """Under torch.distributed.run with a world size other than --gpus, bench.py refuses."""
     r = _bench(["--gpus", "2", "--n", "4096"], {"WORLD_SIZE": "1"})
     assert r.returncode != 0 and "--gpus 2 but WORLD_SIZE=1" in r.stderr
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_dumps_last_step(tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` times K steps and reports
+    only the headline figure (what --full adds is absent); --dump-outputs writes
+    the last timed step's accept bits, one float32 per signature, equal to the
+    construction's mask (seeded: the same in every run)."""
+    import json
+    import subprocess
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import synth
+    n = 10_000  # no multiple of the 512-signature group, nor of 8
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2",
+                        "--n", str(n), "--dump-outputs", str(tmp_path / "out")], env=env, capture_output=True,
+                       text=True, timeout=240)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line["steps"] == 3 and line["check"] == "pass" and line["unit"] == "verifies/s"
+    assert line["ms_per_step"] > 0 and abs(line["value"] - n / (line["ms_per_step"] * 1e-3)) <= 1e-6 * line["value"]
+    for key in ("kernels", "roofline", "ms_per_step_one_stream", "host_path", "qc_latency_us", "cpu_baseline",
+                "other_configs"):
+        assert key not in line, key
+    assert sorted(os.listdir(tmp_path / "out")) == ["accept.npy"]
+    got = np.load(tmp_path / "out" / "accept.npy")
+    ok = synth.config4(n, n_keys=100, seed=0x50424654)[4]
+    assert got.dtype == np.float32 and got.shape == (n,)
+    assert (got == ok.astype(np.float32)).all() and 0 < (got == 0).sum() == round(0.01 * n)
 
 
 def test_bench_numa_pinning_helpers(monkeypatch):

@@ -5,7 +5,7 @@
 #   bash tools/ab.sh OUT ROUNDS WORKLOADS VARIANT [VARIANT ...]
 #
 # WORKLOADS: comma-separated, each one of
-#   bench:N     bench.py --no-extras --n N --steps 30  (verifies/s, comb/scalar ms)
+#   bench:N     bench.py --full --no-extras --n N --steps 30  (verifies/s, comb/scalar ms)
 #   streams:N:S the same with --streams S
 #   sha         bench.py --sha-only                      (config 5 + PBFT digests)
 #   qc          tools/qc_ab.py      (QC p50, fresh certificates)
@@ -38,8 +38,8 @@ run() {  # run WORKLOAD VARIANT FILE
   done
   local cmd
   case "$w" in
-    bench:*) cmd=(python3 bench.py --no-extras --n "${w#bench:}" --steps 30) ;;
-    streams:*) local a=${w#streams:}; cmd=(python3 bench.py --no-extras --n "${a%%:*}" --streams "${a##*:}" --steps 50) ;;
+    bench:*) cmd=(python3 bench.py --full --no-extras --n "${w#bench:}" --steps 30) ;;
+    streams:*) local a=${w#streams:}; cmd=(python3 bench.py --full --no-extras --n "${a%%:*}" --streams "${a##*:}" --steps 50) ;;
     sha) cmd=(python3 bench.py --sha-only) ;;
     qc) cmd=(python3 tools/qc_ab.py) ;;
     tick) cmd=(python3 -u tools/qc_cadence.py --parts tick) ;;

@@ -8,7 +8,7 @@ ROOT=$(pwd)
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 cd /tmp
-timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$ROOT/$OUT/trace" -o run -- python3 "$ROOT/bench.py" --no-extras \
+timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$ROOT/$OUT/trace" -o run -- python3 "$ROOT/bench.py" --full --no-extras \
   > "$ROOT/$OUT/bench_under_rocprof.json" 2> "$ROOT/$OUT/trace.log" || { echo "trace failed"; tail -20 "$ROOT/$OUT/trace.log"; exit 1; }
 cat "$ROOT/$OUT/bench_under_rocprof.json"
 cd "$ROOT"

@@ -7,7 +7,7 @@
 #   tests          the full -m gpu suite               -> OUT/gpu_tests.log
 #   tests:EXPR     the -m gpu tests selected by -k EXPR -> OUT/gpu_tests_k.log
 #   smoke          __graft_entry__.smoke()             -> OUT/smoke.log
-#   bench          bench.py, default arguments         -> OUT/bench.json
+#   bench          bench.py --full                     -> OUT/bench.json
 #   qc             tools/qc_fresh.py 4000              -> OUT/qc_fresh.json
 #   cadence[:P]    tools/qc_cadence.py --parts P       -> OUT/cadence.jsonl
 #   profile        bench under rocprofv3 + PMC passes  -> OUT/prof/ (tools/profile.sh)
@@ -32,7 +32,7 @@ for step in "$@"; do
         > "$OUT/smoke.log" 2>&1 || { echo "smoke failed"; tail -20 "$OUT/smoke.log"; exit 1; }
       tail -1 "$OUT/smoke.log" ;;
     bench)
-      timeout -k 10 600 python -u bench.py > "$OUT/bench.json" 2> "$OUT/bench.err" \
+      timeout -k 10 600 python -u bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err" \
         || { echo "bench failed"; tail -20 "$OUT/bench.err"; exit 1; }
       tail -c 400 "$OUT/bench.json"; echo ;;
     qc)
