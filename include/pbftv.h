@@ -90,11 +90,23 @@ int pbftv_memset_dev(pbftv_ctx* ctx, int dev, void* dst, int value, uint64_t byt
 /* The context's stream of device dev as a hipStream_t (for *_dev calls). */
 void* pbftv_stream(pbftv_ctx* ctx, int dev);
 int pbftv_stream_sync(pbftv_ctx* ctx, int dev);
-/* Caller streams on device dev for *_dev calls (non-blocking HIP streams).  A
- * stream made here owns its ECDSA verify scratch (stage-1 records, key order,
- * result bytes; freed by pbftv_stream_destroy), so verifies enqueued on two
+/* Caller streams on device dev for *_dev calls.  A stream made here owns its
+ * ECDSA verify scratch (stage-1 records, key order, result bytes; freed by
+ * pbftv_stream_destroy) AND a hardware queue, so verifies enqueued on two
  * such streams run concurrently on the GPU: a caller that alternates batches
  * between two streams overlaps batch j + 1's scalar stage with batch j's comb.
+ * That is how consecutive batches overlap; batches on one stream, or on
+ * streams that share a hardware queue, run strictly one after the other.
+ * The queue is the stream's alone whatever other streams the process has
+ * (the HIP runtime spreads plain streams over GPU_MAX_HW_QUEUES = 4 queues
+ * and shares them beyond that; these streams are created with a CU mask of
+ * every CU, which the runtime never pools).  At most 8 streams per device
+ * and context hold such a queue at a time; the ones created beyond that are
+ * plain non-blocking streams and may share.  A stream with a queue of its own
+ * is a blocking HIP stream: it orders with work on the null stream, which the
+ * library never uses -- keep a caller's null-stream work off the hot path.
+ * PBFTV_STREAM_QUEUE=shared (read once per process) makes every stream plain,
+ * as before.
  * Other device scratch shared by calls on different streams (d.stream and any
  * foreign hipStream_t) is ordered by the library (an event per device), so
  * concurrent *_dev calls on several streams are safe. */

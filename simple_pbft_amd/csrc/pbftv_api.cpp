@@ -318,6 +318,10 @@ struct Device {
   // verifies on two such streams run concurrently (batch j + 1's scalar stage
   // in the wave slots batch j's comb leaves free) instead of queueing on d.vs
   std::map<hipStream_t, std::unique_ptr<VerifyScratch>> stream_scratch;
+  // those of them that hold a hardware queue of their own (own_queue_stream):
+  // at most kOwnQueues, the streams created past that are plain and may share
+  static constexpr size_t kOwnQueues = 8;
+  std::set<hipStream_t> own_queue;
   // caller streams the library did not create that a wave-path verify (no
   // device scratch, so no scratch_ev fence) was enqueued on since the last key
   // change: an event recorded after each such enqueue (events stay valid when
@@ -334,13 +338,54 @@ struct Device {
 
 // key-order scratch: a fresh allocation gets its header zeroed (the sort's
 // kernels leave it zero after every batch; p256_kernels.hip k_key_hist).
-// st == nullptr: a blocking memset.
-hipError_t ensure_key_sort(VerifyScratch& sc, uint64_t n, uint32_t nkeys, hipStream_t st) {
+// wait: the memset has completed on return.  Never the null stream: using it
+// once costs the process a hardware queue for good, and a null-stream
+// operation waits for every blocking stream on the GPU.
+hipError_t ensure_key_sort(VerifyScratch& sc, uint64_t n, uint32_t nkeys, hipStream_t st, bool wait = false) {
   const size_t cap0 = sc.ksort.cap;
   hipError_t e = sc.ksort.ensure(pbftv::key_sort_scratch_bytes(n, nkeys));
   if (e != hipSuccess || sc.ksort.cap == cap0) return e;
-  return st ? hipMemsetAsync(sc.ksort.p, 0, pbftv::key_sort_header_bytes(), st)
-            : hipMemset(sc.ksort.p, 0, pbftv::key_sort_header_bytes());
+  e = hipMemsetAsync(sc.ksort.p, 0, pbftv::key_sort_header_bytes(), st);
+  return e != hipSuccess || !wait ? e : hipStreamSynchronize(st);
+}
+
+// PBFTV_STREAM_QUEUE=shared (read once): the streams below are plain
+// non-blocking streams again, which the runtime spreads over
+// GPU_MAX_HW_QUEUES hardware queues shared by all of them.
+bool stream_queue_shared() {
+  static const bool shared = [] {
+    const char* e = getenv("PBFTV_STREAM_QUEUE");
+    return e && std::strcmp(e, "shared") == 0;
+  }();
+  return shared;
+}
+
+// A stream whose work must run BESIDE another stream's (two batch streams:
+// batch j + 1's scalar stage beside batch j's comb; stream2: the odd host
+// chunks beside the even ones) needs a hardware queue to itself: two streams
+// on one queue run strictly in order.  The runtime gives the process
+// GPU_MAX_HW_QUEUES (4) queues for ALL its normal-priority streams, and the
+// context's own (stream, astream, cstream, lstream) take them first, so a
+// plain batch stream shares one sooner or later (round 6: the fifth stream,
+// profiles/r07_overlap_before.txt).  A stream created with a CU mask is never
+// pooled (tools/hiq_share.hip, profiles/r06_hiq_share.txt); the mask here has
+// every CU set, so where its kernels run does not change.  *own: whether the
+// stream got such a queue (want_own false, the knob, or the call failed: a
+// plain stream).  A CU-masked stream is a blocking stream: it orders with the
+// null stream, which the library itself never uses.
+hipError_t own_queue_stream(int dev, bool want_own, hipStream_t* st, bool* own) {
+  *own = false;
+  int ncu = 0;
+  if (want_own && !stream_queue_shared() &&
+      hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && ncu > 0) {
+    const std::vector<uint32_t> mask((ncu + 31) / 32, 0xFFFFFFFFu);
+    if (hipExtStreamCreateWithCUMask(st, (uint32_t)mask.size(), mask.data()) == hipSuccess) {
+      *own = true;
+      return hipSuccess;
+    }
+    (void)hipGetLastError();  // (the plain stream below is the answer, not this error)
+  }
+  return hipStreamCreateWithFlags(st, hipStreamNonBlocking);
 }
 
 // before / after enqueueing work that uses the device scratch on stream st.
@@ -1257,6 +1302,7 @@ void pbftv_close(pbftv_ctx* ctx) {
       kv.second->release();
     }
     d->stream_scratch.clear();
+    d->own_queue.clear();
     if (d->join_ev) (void)hipEventDestroy(d->join_ev);
     d->keys_all.release();
     if (d->cstream) {
@@ -1310,7 +1356,7 @@ int pbftv_reserve(pbftv_ctx* ctx, uint64_t n) {
     HIP_TRY(d.vs.rec.ensure(pbftv::ecdsa_record_bytes(n)));
     HIP_TRY(d.vs.prefix.ensure(pbftv::scalar_prefix_bytes(n)));
     if (pbftv::key_sort_wanted(n, d.nkeys)) {
-      HIP_TRY(ensure_key_sort(d.vs, n, d.nkeys, nullptr));
+      HIP_TRY(ensure_key_sort(d.vs, n, d.nkeys, d.stream, true));
       HIP_TRY(d.vs.okb.ensure(n));
     }
   }
@@ -1522,9 +1568,11 @@ int pbftv_stream_create(pbftv_ctx* ctx, int dev, void** out_stream) {
   if (!d || !out_stream) return fail(PBFTV_EINVAL, "bad context, device index or out pointer");
   HIP_TRY(hipSetDevice(d->id));
   hipStream_t st;
-  HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
   {
     std::lock_guard<std::mutex> lk(d->mu);
+    bool own = false;
+    HIP_TRY(own_queue_stream(d->id, d->own_queue.size() < Device::kOwnQueues, &st, &own));
+    if (own) d->own_queue.insert(st);
     d->stream_scratch[st] = std::make_unique<VerifyScratch>();
   }
   *out_stream = reinterpret_cast<void*>(st);
@@ -1544,6 +1592,7 @@ int pbftv_stream_destroy(pbftv_ctx* ctx, int dev, void* stream) {
       it->second->release();
       d->stream_scratch.erase(it);
     }
+    d->own_queue.erase(st);
   }
   HIP_TRY(hipStreamDestroy(st));
   return PBFTV_OK;
@@ -2108,7 +2157,10 @@ static int verify_host_pipelined(Device& d, const uint8_t* H, const uint8_t* S, 
   const bool keys_first = env_flag("PBFTV_HOST_KEYS_FIRST", true);
   const bool two = env_flag("PBFTV_HOST_2COMPUTE", true) && nch > 1;
   if (two) {
-    if (!d.stream2) HIP_TRY(hipStreamCreateWithFlags(&d.stream2, hipStreamNonBlocking));
+    if (!d.stream2) {  // (a queue of its own beside the kOwnQueues of the batch streams)
+      bool own = false;
+      HIP_TRY(own_queue_stream(d.id, true, &d.stream2, &own));
+    }
     if (!d.join_ev) HIP_TRY(hipEventCreateWithFlags(&d.join_ev, hipEventDisableTiming));
   }
   if (!d.cstream) HIP_TRY(hipStreamCreateWithFlags(&d.cstream, hipStreamNonBlocking));
