@@ -80,8 +80,13 @@ int pbftv_dev_free(pbftv_ctx* ctx, int dev, void* ptr);
 /* Pinned host memory (hipHostMalloc, portable): batches placed in it skip the
  * staging copy of the host-buffer verify path (e.g. a cgo shim's pool-flush
  * buffers).  A freed block is kept for the next pbftv_host_alloc of a similar
- * size (up to 1 GiB per context; released at pbftv_close), so a free does
- * not synchronise the GPU either. */
+ * size (at least the size asked for and at most twice it; up to 1 GiB of
+ * freed blocks per context, the largest leave first; released at
+ * pbftv_close), so a free does not synchronise the GPU either.  Before
+ * pbftv_host_free the caller must have synchronised its own asynchronous use
+ * of the block (a *_dev call or a copy of its own that still reads or writes
+ * it): the block may be handed out again, or unmapped, at once.  The library's
+ * own calls that read a host buffer have finished with it when they return. */
 int pbftv_host_alloc(pbftv_ctx* ctx, uint64_t bytes, void** out_ptr);
 int pbftv_host_free(pbftv_ctx* ctx, void* ptr);
 int pbftv_memcpy_h2d(pbftv_ctx* ctx, int dev, void* dst, const void* src, uint64_t bytes);
@@ -205,6 +210,13 @@ int pbftv_qc_stamps_all(pbftv_ctx* ctx, int dev, uint64_t* out, uint32_t waves);
  * out[5] armings, out[6] keeper rotations, out[7] the armed kernel now: its
  * workgroups (0: none armed) | 1 << 32 if it is the wide one. */
 int pbftv_qc_counters(pbftv_ctx* ctx, int dev, uint64_t out[8]);
+/* Counters of the library's own bookkeeping on device dev since pbftv_open
+ * (diagnostics; tests assert on them): out[0] pbftv_dev_free blocks still
+ * waiting for their marks, out[1] events held by them, out[2] spare events,
+ * out[3] events created for such marks (at every call out[1] + out[2] ==
+ * out[3]), out[4] lane-path ECDSA batches that took the key order; out[5..7]
+ * are zero. */
+int pbftv_lib_counters(pbftv_ctx* ctx, int dev, uint64_t out[8]);
 
 /* ---- SHA-256 digests (utils.Hash) ------------------------------------ */
 

@@ -30,6 +30,7 @@
 #include "../../include/pbftv.h"
 #include "gojson.h"
 #include "gojson_enc.h"
+#include "host/pending_frees.h"
 #include "kernels.h"
 
 namespace {
@@ -307,6 +308,8 @@ struct Device {
   std::set<void*> pool_ptrs;
   std::vector<PendingFree> pending_frees;
   std::vector<hipEvent_t> spare_ev;
+  uint64_t ev_created = 0;  // marks ever created: each is in one pending free or in spare_ev (pbftv_lib_counters)
+  std::atomic<uint64_t> sorted_batches{0};  // lane-path batches that took the key order
   // Device scratch (rec, prefix, ksort, okb, order_scratch) is shared by
   // calls on d.stream and on caller streams (the *_dev entry points).  The
   // mutex orders the enqueues; this event orders the execution: a call on a
@@ -1273,6 +1276,9 @@ void pbftv_close(pbftv_ctx* ctx) {
     qc_unregister(*d);
     (void)qc_streams_release(*d);
     (void)hipStreamSynchronize(d->stream);
+    // batches still queued on the caller's library streams read the key tables
+    // and their scratch: they finish before anything below is freed
+    for (auto& kv : d->stream_scratch) (void)hipStreamSynchronize(kv.first);
     (void)collect_times(*d);
     for (auto& b : d->qblocks) b->release();
     for (auto& b : d->tab_scratch) b.release();
@@ -1316,14 +1322,17 @@ void pbftv_close(pbftv_ctx* ctx) {
     }
     if (d->pool) {  // pending frees and blocks the caller did not free go with the context
       GpuQuiesce quiet(d->id);
-      for (auto& pf : d->pending_frees) {
-        for (hipEvent_t e : pf.ev) {
-          (void)hipEventSynchronize(e);
-          d->spare_ev.push_back(e);
-        }
-        (void)hipFreeAsync(pf.p, d->astream);
-      }
-      d->pending_frees.clear();
+      (void)pbftv::reap_pending(
+          d->pending_frees,
+          [](hipEvent_t e) {
+            (void)hipEventSynchronize(e);
+            return pbftv::MarkState::kPassed;
+          },
+          [&](Device::PendingFree& pf) { d->spare_ev.insert(d->spare_ev.end(), pf.ev.begin(), pf.ev.end()); },
+          [&](Device::PendingFree& pf) {
+            (void)hipFreeAsync(pf.p, d->astream);
+            return true;
+          });
       for (void* p : d->pool_ptrs) (void)hipFreeAsync(p, d->astream);
       d->pool_ptrs.clear();
       (void)hipStreamSynchronize(d->astream);
@@ -1411,39 +1420,43 @@ static hipError_t defer_free(Device& d, void* p) {
       d.spare_ev.pop_back();
     } else {
       HIP_TRY_E(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+      ++d.ev_created;
     }
     pf.ev.push_back(e);
     return hipEventRecord(e, st);
   };
+  hipError_t err = hipSuccess;
   for (hipStream_t st : {d.stream, d.stream2, d.cstream, d.lstream})
-    if (st) HIP_TRY_E(mark(st));
-  for (auto& kv : d.stream_scratch) HIP_TRY_E(mark(kv.first));
+    if (st && err == hipSuccess) err = mark(st);
+  for (auto& kv : d.stream_scratch)
+    if (err == hipSuccess) err = mark(kv.first);
+  if (err != hipSuccess) {  // the free did not happen: its marks go back, the caller keeps the block
+    d.spare_ev.insert(d.spare_ev.end(), pf.ev.begin(), pf.ev.end());
+    return err;
+  }
   d.pending_frees.push_back(std::move(pf));
   return hipSuccess;
 }
 
-// return the blocks whose marks have all passed to the pool (host polls)
+// return the blocks whose marks have all passed to the pool (host polls);
+// the list logic is host/pending_frees.h
 static hipError_t reap_frees(Device& d) {
-  size_t k = 0;
-  for (auto& pf : d.pending_frees) {
-    bool done = true;
-    for (hipEvent_t e : pf.ev) {
-      const hipError_t q = hipEventQuery(e);
-      if (q == hipErrorNotReady) {
-        done = false;
-        break;
-      }
-      if (q != hipSuccess) return q;
-    }
-    if (!done) {
-      d.pending_frees[k++] = std::move(pf);
-      continue;
-    }
-    for (hipEvent_t e : pf.ev) d.spare_ev.push_back(e);
-    HIP_TRY_E(hipFreeAsync(pf.p, d.astream));
-  }
-  d.pending_frees.resize(k);
-  return hipSuccess;
+  hipError_t err = hipSuccess;
+  (void)pbftv::reap_pending(
+      d.pending_frees,
+      [&](hipEvent_t e) {
+        const hipError_t q = hipEventQuery(e);
+        if (q == hipSuccess) return pbftv::MarkState::kPassed;
+        if (q == hipErrorNotReady) return pbftv::MarkState::kNotReady;
+        err = q;
+        return pbftv::MarkState::kError;
+      },
+      [&](Device::PendingFree& pf) { d.spare_ev.insert(d.spare_ev.end(), pf.ev.begin(), pf.ev.end()); },
+      [&](Device::PendingFree& pf) {
+        err = hipFreeAsync(pf.p, d.astream);
+        return err == hipSuccess;
+      });
+  return err;
 }
 
 int pbftv_dev_alloc(pbftv_ctx* ctx, int dev, uint64_t bytes, void** out_ptr) {
@@ -1521,8 +1534,8 @@ int pbftv_dev_free(pbftv_ctx* ctx, int dev, void* ptr) {
   if (it != d->pool_ptrs.end()) {
     // the block returns to the pool once the context's work queued so far
     // has passed (defer_free / reap_frees)
+    HIP_TRY(defer_free(*d, ptr));  // (on an error it is still the caller's block)
     d->pool_ptrs.erase(it);
-    HIP_TRY(defer_free(*d, ptr));
     HIP_TRY(reap_frees(*d));
     return PBFTV_OK;
   }
@@ -2072,6 +2085,7 @@ static int verify_on_device(Device& d, const uint8_t* d_hashes, const uint8_t* d
   const bool sorted = pbftv::key_sort_wanted(n, d.nkeys);
   pbftv::KeyOrder ko{nullptr, nullptr, 0};
   if (sorted) {
+    d.sorted_batches.fetch_add(1, std::memory_order_relaxed);
     HIP_TRY(sc.okb.ensure(n));  // comb lanes in key order: a wave's table lookups share keys (p256_kernels.hip k_key_*)
     HIP_TRY(ensure_key_sort(sc, n, d.nkeys, st));
     HIP_TRY(pbftv::launch_key_count(d_key_idx, n, d.nkeys, sc.ksort.p, sc.sort_parity++, &ko, st));
@@ -2538,6 +2552,19 @@ int pbftv_qc_counters(pbftv_ctx* ctx, int dev, uint64_t out[8]) {
   out[5] = d->qc_armings;
   out[6] = d->rotations;
   out[7] = d->arm_seq ? (uint64_t)d->arm_waves | ((uint64_t)(d->arm_wide ? 1 : 0) << 32) : 0;
+  return PBFTV_OK;
+}
+
+int pbftv_lib_counters(pbftv_ctx* ctx, int dev, uint64_t out[8]) {
+  Device* d = dev_of(ctx, dev);
+  if (!d || !out) return fail(PBFTV_EINVAL, "bad context, device index or out pointer");
+  std::lock_guard<std::mutex> lk(d->mu);
+  std::memset(out, 0, 8 * sizeof(uint64_t));
+  out[0] = d->pending_frees.size();
+  for (const auto& pf : d->pending_frees) out[1] += pf.ev.size();
+  out[2] = d->spare_ev.size();
+  out[3] = d->ev_created;
+  out[4] = d->sorted_batches.load(std::memory_order_relaxed);
   return PBFTV_OK;
 }
 

@@ -76,6 +76,7 @@ def lib() -> ctypes.CDLL:
         "pbftv_set_latency_path_max": (ctypes.c_int, [_vp, ctypes.c_uint64]),
         "pbftv_qc_stamps_all": (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_uint32]),
         "pbftv_qc_counters": (ctypes.c_int, [_vp, ctypes.c_int, _vp]),
+        "pbftv_lib_counters": (ctypes.c_int, [_vp, ctypes.c_int, _vp]),
         "pbftv_hash_hex": (ctypes.c_int, [_vp, _vp, ctypes.c_uint64, ctypes.c_char_p]),
         "pbftv_sha256_batch": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_uint64, _vp]),
         "pbftv_digest_check_batch": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, ctypes.c_uint64, _vp]),
@@ -584,6 +585,16 @@ class Verifier:
         r["armed_waves"] = int(o[7]) & 0xFFFFFFFF
         r["armed_wide"] = bool(int(o[7]) >> 32)
         return r
+
+    def lib_counters(self, dev: int = 0) -> dict:
+        """pbftv_lib_counters: frees waiting for their marks, the events they
+        hold, spare events, events created (held + spare == created), and the
+        lane-path batches that took the key order, since the context opened."""
+        o = np.zeros(8, np.uint64)
+        _check(self._L.pbftv_lib_counters(self._h, dev, o.ctypes.data))
+        assert not o[5:].any()
+        names = ("pending_frees", "held_events", "spare_events", "events_created", "sorted_batches")
+        return {k: int(v) for k, v in zip(names, o[:5])}
 
     def qc_stamps(self, dev: int = 0) -> dict:
         """pbftv_qc_stamps: where the last latency-path call's time went (host
