@@ -853,8 +853,14 @@ PBFTV_HD void sums_chunk(uint32_t* out, int cnt, bool has_h, const uint32_t hw[1
   batch_to_affine(out, cnt, st, ld);
 }
 
-// Whole table of one base on the CPU harness (tests) -- the device runs the
-// same phases as separate kernels (p256_kernels.hip).
+// Whole table of one base on the CPU harness (tests).  The device build
+// (p256_kernels.hip k_tab_bases / k_tab_small / k_tab_entries) has the same
+// three phases and the same table layout, but it is other code: there CL is
+// 2^(kW/2) above 16 bits (TabGeom; always 256 here), the H rows are walked in
+// segments of 64, phase 3 is an affine addition in signed limbs over chunks of
+// 256 entries with one shared inversion (here: jac_madd<true> per entry) and
+// is launched in slices of 2^18 lanes.  So this function says nothing about
+// the device's tables; tests/test_gpu_tables.py checks those at their seams.
 template <int W, class StoreF, class LoadF>
 PBFTV_HD void build_table_serial(uint32_t* table, const fe& bx, const fe& by, uint32_t* lbuf, uint32_t* hbuf,
                                  StoreF st, LoadF ld) {
