@@ -8,7 +8,7 @@
 #include <cstdio>
 #include <cstdlib>
 
-#include "fe29.h"
+#include "fes.h"
 
 using namespace pbftv;
 
@@ -20,7 +20,25 @@ __device__ __forceinline__ void mul_v(fe& r, const fe& a, const fe& b) {
   if constexpr (V == 0) fe_mul(r, a, b);
   else if constexpr (V == 1) fe_mul_rows_then_reduce(r, a, b);
   else if constexpr (V == 2) fe_sqr(r, a);
-  else fe_sqr_il(r, a);
+  else if constexpr (V == 3) fe_sqr_il(r, a);
+  // signed-limb products (fes.h): the kept row schedule against the column-order upper half
+  else if constexpr (V == 4) fs_mul_rows(r, a, b);
+  else if constexpr (V == 5) fs_mul(r, a, b);
+  else if constexpr (V == 6) fs_sqr_rows(r, a);
+  else fs_sqr(r, a);
+}
+
+// the products of three and four operands: a is the chain, c the chain's value
+// of the iteration before (so that no product of two operands stays the same
+// from one iteration to the next and leaves the loop), b and d are fixed
+template <int V>
+__device__ __forceinline__ void mul_w(fe& r, const fe& a, const fe& b, const fe& c, const fe& d) {
+  if constexpr (V == 8) fs_sqr_sub2_rows(r, a, b, c);
+  else if constexpr (V == 9) fs_sqr_sub2(r, a, b, c);
+  else if constexpr (V == 10) fs_mul2_add_rows(r, a, b, c, d);
+  else if constexpr (V == 11) fs_mul2_add(r, a, b, c, d);
+  else if constexpr (V == 12) fs_sqr_mul_add_rows(r, a, b, c);
+  else fs_sqr_mul_add(r, a, b, c);
 }
 
 // occupancy limited by dynamic LDS: lds_bytes per 256-thread block
@@ -32,8 +50,24 @@ __global__ void __launch_bounds__(256) kbench(const uint32_t* __restrict__ in, u
   for (int l = 0; l < 9; ++l) b.v[l] = in[(lane * 7 + l) & 1023] & kMask29;
   for (int k = 0; k < K; ++k)
     for (int l = 0; l < 9; ++l) a[k].v[l] = in[(lane * 3 + 11 * k + l) & 1023] & kMask29;
-  for (int i = 0; i < iters; ++i) {
-    PBFTV_UNROLL for (int k = 0; k < K; ++k) mul_v<V>(a[k], a[k], b);
+  if constexpr (V < 8) {
+    for (int i = 0; i < iters; ++i) {
+      PBFTV_UNROLL for (int k = 0; k < K; ++k) mul_v<V>(a[k], a[k], b);
+    }
+  } else {
+    fe c[K], d;
+    for (int l = 0; l < 9; ++l) d.v[l] = in[(lane * 5 + 101 + l) & 1023] & (l < 8 ? kMask29 : 0xFFFFFFu);
+    b.v[8] &= 0xFFFFFFu;
+    for (int k = 0; k < K; ++k)
+      for (int l = 0; l < 9; ++l) c[k].v[l] = in[(lane * 13 + 7 * k + 211 + l) & 1023] & (l < 8 ? kMask29 : 0xFFFFFFu);
+    for (int i = 0; i < iters; ++i) {
+      PBFTV_UNROLL for (int k = 0; k < K; ++k) {
+        const fe t = a[k];
+        mul_w<V>(a[k], t, b, c[k], d);
+        c[k] = t;
+      }
+    }
+    for (int k = 0; k < K; ++k) a[k].v[0] ^= c[k].v[3];
   }
   uint32_t x = 0;
   for (int k = 0; k < K; ++k)
@@ -61,7 +95,7 @@ static void run(const char* name, const uint32_t* in, uint32_t* out, int waves_p
   CHECK(hipEventElapsedTime(&ms, a, b));
   const double waves = blocks * 4.0;
   const double cyc = ms * 1e-3 * 2.4e9 * 1024.0 / (waves * iters * K);
-  printf("%-12s K=%d waves/SIMD=%d: %8.3f ms  %6.0f SIMD-cycles per wave-op\n", name, K, waves_per_simd, ms, cyc);
+  printf("%-19s K=%d waves/SIMD=%d: %8.3f ms  %6.0f SIMD-cycles per wave-op\n", name, K, waves_per_simd, ms, cyc);
 }
 
 template <int V>
@@ -85,5 +119,15 @@ int main() {
   sweep<1>("fe_mul_rows_then_reduce", in, out);
   sweep<2>("fe_sqr", in, out);
   sweep<3>("fe_sqr_il", in, out);
+  sweep<4>("fs_mul_rows", in, out);
+  sweep<5>("fs_mul", in, out);
+  sweep<6>("fs_sqr_rows", in, out);
+  sweep<7>("fs_sqr", in, out);
+  sweep<8>("fs_sqr_sub2_rows", in, out);
+  sweep<9>("fs_sqr_sub2", in, out);
+  sweep<10>("fs_mul2_add_rows", in, out);
+  sweep<11>("fs_mul2_add", in, out);
+  sweep<12>("fs_sqr_mul_add_rows", in, out);
+  sweep<13>("fs_sqr_mul_add", in, out);
   return 0;
 }

@@ -23,6 +23,28 @@ __device__ __forceinline__ void ld_entry(const uint4* __restrict__ tab, int k, f
   entry_to_fe(x, y, w);
 }
 
+// the comb's step on the kept row-schedule products (fes.h *_rows): what
+// xyzz_madd_s_flip ran before the column-order upper half
+__device__ __forceinline__ void step_rows(xyzz_s& acc, const fe& x2, const fe& y2) {
+  fe u2, s2, p, r, pp, ppp, q, t;
+  fs_mul_rows(u2, x2, acc.zz);
+  fs_mul_rows(s2, y2, acc.zzz);
+  fs_sub(p, u2, acc.x);
+  fs_sub(r, s2, acc.y);
+  fs_sqr_rows(pp, p);
+  fs_mul_rows(ppp, p, pp);
+  fs_mul_rows(q, acc.x, pp);
+  fe x3;
+  fs_sqr_sub2_rows(x3, r, ppp, q);
+  fs_sub(t, x3, q);
+  fs_mul2_add_rows(acc.y, r, t, acc.y, ppp);
+  fs_mul_rows(acc.zz, acc.zz, pp);
+  fs_mul_rows(acc.zzz, acc.zzz, ppp);
+  acc.x = x3;
+}
+
+// V: 0 jacobian, 1 xyzz unsigned, 2 xyzz signed, 3..5 the comb's own step on
+// the row-schedule products (3), lone column chains (4), paired chains (5)
 template <int V, int WAVES>
 __global__ void __launch_bounds__(256, WAVES) kbench(const uint4* __restrict__ tab, uint32_t* __restrict__ out, int iters) {
   const int lane = blockIdx.x * 256 + threadIdx.x;
@@ -46,7 +68,7 @@ __global__ void __launch_bounds__(256, WAVES) kbench(const uint4* __restrict__ t
       xyzz_madd_s(acc, ex, ey);
     }
     for (int l = 0; l < 9; ++l) out[lane * 9 + l] = acc.x.v[l] ^ acc.zz.v[l] ^ acc.y.v[l] ^ acc.zzz.v[l];
-  } else if constexpr (V == 3) {
+  } else if constexpr (V >= 3) {
     // the comb's own step (comb_step_s's body): the y negation folded into
     // the entry unpacking, the W = sigma Y accumulator
     xyzz_s acc;
@@ -58,7 +80,9 @@ __global__ void __launch_bounds__(256, WAVES) kbench(const uint4* __restrict__ t
       uint32_t w[16] = {e0.x, e0.y, e0.z, e0.w, e1.x, e1.y, e1.z, e1.w, e2.x, e2.y, e2.z, e2.w, e3.x, e3.y, e3.z, e3.w};
       fe ex, ey;
       entry_to_fe_cneg(ex, ey, w, ((lane + i) & 1) != neg);
-      xyzz_madd_s_flip(acc, ex, ey);
+      if constexpr (V == 3) step_rows(acc, ex, ey);
+      else if constexpr (V == 4) xyzz_madd_s_flip_lone(acc, ex, ey);
+      else xyzz_madd_s_flip_pair(acc, ex, ey);
       neg = !neg;
     }
     for (int l = 0; l < 9; ++l) out[lane * 9 + l] = acc.x.v[l] ^ acc.zz.v[l] ^ acc.y.v[l] ^ acc.zzz.v[l];
@@ -89,8 +113,13 @@ static void run(const char* name, const uint4* tab, uint32_t* out, int blocks, i
   CHECK(hipEventElapsedTime(&ms, a, b));
   const double waves = blocks * 4.0;
   const double cyc = ms * 1e-3 * 2.4e9 * 1024.0 / (waves * iters);
-  printf("%-24s waves/SIMD>=%d blocks %6d: %8.3f ms  %7.0f SIMD-cycles per wave-addition  %.1f M adds/s\n", name,
-         WAVES, blocks, ms, cyc, blocks * 256.0 * iters / (ms * 1e-3) / 1e6);
+  // checksum of the first 4096 lanes' outputs: the three step variants must agree
+  static uint32_t h[4096 * 9];
+  CHECK(hipMemcpy(h, out, sizeof(h), hipMemcpyDeviceToHost));
+  uint32_t sum = 0;
+  for (uint32_t w : h) sum = sum * 31u + w;
+  printf("%-24s waves/SIMD>=%d blocks %6d: %8.3f ms  %7.0f SIMD-cycles per wave-addition  %.1f M adds/s  sum %08x\n",
+         name, WAVES, blocks, ms, cyc, blocks * 256.0 * iters / (ms * 1e-3) / 1e6, sum);
 }
 
 int main() {
@@ -119,7 +148,16 @@ int main() {
   run<2, 2>("madd-2008-s xyzz signed", tab, out, blocks, iters);
   run<2, 3>("madd-2008-s xyzz signed", tab, out, blocks, iters);
   run<2, 4>("madd-2008-s xyzz signed", tab, out, blocks, iters);
-  run<3, 2>("comb step (flip, cneg)", tab, out, blocks, iters);
-  run<3, 4>("comb step (flip, cneg)", tab, out, blocks, iters);
+  for (int rep = 0; rep < 3; ++rep) {
+    run<3, 1>("comb step, rows", tab, out, blocks, iters);
+    run<4, 1>("comb step, lone columns", tab, out, blocks, iters);
+    run<5, 1>("comb step, paired", tab, out, blocks, iters);
+    run<3, 2>("comb step, rows", tab, out, blocks, iters);
+    run<4, 2>("comb step, lone columns", tab, out, blocks, iters);
+    run<5, 2>("comb step, paired", tab, out, blocks, iters);
+    run<3, 4>("comb step, rows", tab, out, blocks, iters);
+    run<4, 4>("comb step, lone columns", tab, out, blocks, iters);
+    run<5, 4>("comb step, paired", tab, out, blocks, iters);
+  }
   return 0;
 }
