@@ -293,6 +293,28 @@ func (x *Ctx) VerifySigs(hashes [][32]byte, sigs [][64]byte, keyIdx []uint32) ([
 	return bits(bm, n), nil
 }
 
+// VerifyPubkeyBatch: crypto/ecdsa.Verify(pubXY[i], hashes[i], r_i, s_i) for
+// every i, each signature under the key that comes with it (X||Y big-endian):
+// for signers that were never registered, such as the clients of request
+// messages.  A key that is not a point of the curve gives false, not an error.
+// No RegisterKeys call is needed and the registered keys are not touched.
+func (x *Ctx) VerifyPubkeyBatch(hashes [][32]byte, sigs [][64]byte, pubXY [][64]byte) ([]bool, error) {
+	n := len(hashes)
+	if len(sigs) != n || len(pubXY) != n {
+		return nil, &Error{Code: EINVAL, Msg: "hashes, sigs and pubXY differ in length"}
+	}
+	if n == 0 {
+		return nil, nil
+	}
+	bm := make([]byte, (n+7)/8)
+	err := call(func() C.int { return C.pbftv_ecdsa_p256_verify_pubkey_batch(x.c, (*C.uint8_t)(unsafe.Pointer(&hashes[0])),
+		(*C.uint8_t)(unsafe.Pointer(&sigs[0])), (*C.uint8_t)(unsafe.Pointer(&pubXY[0])), C.uint64_t(n), u8(bm)) })
+	if err != nil {
+		return nil, err
+	}
+	return bits(bm, n), nil
+}
+
 // QCVerify verifies one quorum certificate and counts it: reached =
 // accepted >= quorum (quorum = 2f reproduces prepared()/committed(),
 // pbft/consensus/pbft_impl.go:207-232; 2f+1 checks a PBFT certificate).

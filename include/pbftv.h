@@ -175,13 +175,15 @@ int pbftv_set_latency_path_max(pbftv_ctx* ctx, uint64_t n);
 /* Per-kernel timing with HIP events recorded on the launch stream around every
  * kernel launch while enabled.  kernel: 0 = ecdsa scalars, 1 = ecdsa comb,
  * 2 = sha256, 3 = ecdsa wave-per-signature (small batches), 4 = Go-JSON message
- * encoder (digest / flush batches).  pbftv_kernel_time_ms synchronises the device's stream and
+ * encoder (digest / flush batches), 5 = ecdsa under unregistered keys (the
+ * ladder kernel of pbftv_ecdsa_p256_verify_pubkey_batch).  pbftv_kernel_time_ms synchronises the device's stream and
  * returns the summed milliseconds and the launch count since the last reset. */
 #define PBFTV_K_ECDSA_SCALARS 0
 #define PBFTV_K_ECDSA_COMB 1
 #define PBFTV_K_SHA256 2
 #define PBFTV_K_ECDSA_WAVE 3
 #define PBFTV_K_GOJSON 4
+#define PBFTV_K_ECDSA_VARBASE 5
 int pbftv_set_kernel_timing(pbftv_ctx* ctx, int enable);
 int pbftv_kernel_time_ms(pbftv_ctx* ctx, int dev, int kernel, double* out_ms, uint64_t* out_launches);
 int pbftv_reset_kernel_times(pbftv_ctx* ctx);
@@ -458,6 +460,35 @@ int pbftv_ecdsa_p256_verify_batch(pbftv_ctx* ctx, const uint8_t* hashes, const u
  * d_bitmap: ceil(n/8) B.  Enqueued on stream, not synchronised. */
 int pbftv_ecdsa_p256_verify_batch_dev(pbftv_ctx* ctx, int dev, const uint8_t* d_hashes, const uint8_t* d_sig_rs,
                                       const uint32_t* d_key_idx, uint64_t n, uint8_t* d_bitmap, void* stream);
+
+/* Verify under keys that were NEVER registered: signature i carries its own
+ * public key pub_xy[64 i ..] (X||Y big-endian).  For signers outside the
+ * registered set -- the clients of request and reply messages, an open set --
+ * where a comb table per key (34 MiB and up) cannot pay for itself; a key
+ * that signs many messages is better registered.  Semantics
+ * are exactly those of pbftv_ecdsa_p256_verify_batch (0 < r, s < n, e not
+ * reduced, R = u1 G + u2 Q, reject R = infinity, accept iff R.x mod n == r,
+ * high-S accepted); a signature whose key is not a point of the curve with
+ * 0 <= x, y < p is a 0 bit, never an error.  out_bitmap: LSB-first,
+ * ceil(n/8) bytes, padding bits zero.  n = 0 returns PBFTV_OK and writes
+ * nothing; n >= 2^32 is PBFTV_EINVAL.  Neither call needs, reads or disturbs
+ * the registered key set (there is no PBFTV_ENOKEYS here).  The G table is
+ * the width-16 one (34 MiB) of the per-GPU cache registration uses, built on
+ * first use and kept while the context lives; each lane's table of its own
+ * key lives in a scratch sized by the GPU's resident lanes, not by n
+ * (PBFTV_VARBASE_LANES overrides the lane count).  About 18x the device time
+ * of a registered verify.
+ * The host form shards contiguously over the context's devices, copies in,
+ * verifies and copies the bitmaps back (no chunk overlap).  The _dev form
+ * (hashes/sigs/keys 16-B aligned) is enqueued on `stream` (null: the context
+ * stream) and not synchronised; its in-flight work is counted by the
+ * context's wait before key changes and by pbftv_dev_free like any other
+ * *_dev verify. */
+int pbftv_ecdsa_p256_verify_pubkey_batch(pbftv_ctx* ctx, const uint8_t* hashes, const uint8_t* sig_rs,
+                                         const uint8_t* pub_xy, uint64_t n, uint8_t* out_bitmap);
+int pbftv_ecdsa_p256_verify_pubkey_batch_dev(pbftv_ctx* ctx, int dev, const uint8_t* d_hashes,
+                                             const uint8_t* d_sig_rs, const uint8_t* d_pub_xy, uint64_t n,
+                                             uint8_t* d_bitmap, void* stream);
 
 /* Quorum certificate: verify n signatures and count acceptances.
  * *out_accepted = popcount; *out_quorum = (*out_accepted >= quorum).  With

@@ -187,6 +187,25 @@ struct ArmArgs {
 };
 hipError_t launch_ecdsa_wave_armed(int wg, int wq, const ArmArgs& a, hipStream_t st);
 
+// ---- ECDSA-P256 under unregistered keys (p256_varbase.hip, varbase.h) ----
+// Every signature carries its key (pub_xy: X||Y big-endian, 64 B each, 16-B
+// aligned).  launch_varbase_keys checks the keys into aux (varbase_aux_bytes:
+// validity words, identity indices -- what launch_ecdsa_scalars takes as
+// key_valid / key_idx with nkeys = n, arrival order -- and the keys in
+// Montgomery form); launch_varbase then verifies the stage-1 records against
+// the width-16 G table, `lanes` signatures at a time (varbase_lanes: the
+// resident lanes for a device of `cus` compute units, or PBFTV_VARBASE_LANES;
+// tab: varbase_table_bytes(lanes) of scratch), and writes the LSB-first bitmap.
+constexpr int kVarbaseGBits = 16;
+size_t varbase_aux_bytes(uint64_t n);
+const uint32_t* varbase_valid(const void* aux, uint64_t n);
+const uint32_t* varbase_index(const void* aux, uint64_t n);
+uint64_t varbase_lanes(int cus);
+size_t varbase_table_bytes(uint64_t lanes);
+hipError_t launch_varbase_keys(const uint8_t* pub_xy, uint64_t n, void* aux, hipStream_t st);
+hipError_t launch_varbase(const void* rec, const void* aux, uint64_t n, const uint32_t* gtab, void* tab,
+                          uint64_t lanes, uint8_t* bitmap, hipStream_t st);
+
 // ---- SHA-256 (sha256_kernels.hip) ----
 // data must stay readable 4 bytes past every message end (device allocations are padded).
 // order: optional permutation (lane -> message), used for block-count bucketing.

@@ -185,7 +185,9 @@ PBFTV_HD void xyzz_madd(xyzz& acc, const fe& x2, const fe& y2) {
   acc.x = x3;
 }
 
-// General Jacobian addition r = p + q (both finite).  Same return codes as jac_madd.
+// General Jacobian addition r = p + q (both finite).  Same return codes as
+// jac_madd; !kCheck: no test, a meeting leaves Z3 = Z1 Z2 H == 0 (varbase.h).
+template <bool kCheck = true>
 PBFTV_HD int jac_add(jac& r, const jac& p, const jac& q) {
   fe z1z1, z2z2, u1, u2, s1, s2, h, rr, t, hh, hhh, v;
   fe_sqr(z1z1, p.z);
@@ -198,7 +200,7 @@ PBFTV_HD int jac_add(jac& r, const jac& p, const jac& q) {
   fe_mul(s2, q.y, t);
   fe_sub(h, u2, u1);
   fe_sub(rr, s2, s1);
-  if (fe_is_zero(h)) return fe_is_zero(rr) ? 1 : 2;
+  if (kCheck && fe_is_zero(h)) return fe_is_zero(rr) ? 1 : 2;
   fe_sqr(hh, h);
   fe_mul(hhh, hh, h);
   fe_mul(v, u1, hh);

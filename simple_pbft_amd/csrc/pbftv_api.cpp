@@ -201,12 +201,15 @@ struct HostBuf {
 // the batched inversion, key order, per-signature result bytes).
 struct VerifyScratch {
   DevBuf rec, prefix, ksort, okb;
+  DevBuf vb_aux, vb_tab;     // verify under unregistered keys: checked keys, the lanes' tables (p256_varbase.hip)
   uint32_t sort_parity = 0;  // batches sorted with ksort (launch_key_count's counter sets)
   void release() {
     rec.release();
     prefix.release();
     ksort.release();
     okb.release();
+    vb_aux.release();
+    vb_tab.release();
   }
 };
 
@@ -255,6 +258,12 @@ struct Device {
   // tables live in blocks (one per registration / add_keys call; slots beyond
   // nkeys are spare capacity kept for the next registration at this width).
   std::shared_ptr<DevBuf> gtab;  // shared by every context on this GPU at this width (g_tables)
+  // the width-16 G table of the verify under unregistered keys (the same
+  // cache; taken at the first such call, kept until the context closes) and
+  // the GPU's compute units (its resident lanes)
+  std::shared_ptr<DevBuf> vb_gtab;
+  int vb_cus = 0;
+  DevBuf vb_pub;  // host form: the shard's keys on the device
   DevBuf key_valid, qptrs;
   DevBuf tab_scratch[6];  // table build: bases, L, H, phase-2 / phase-3 scratch, table addresses
   DevBuf tab_keys;        // table build: the keys' coordinates
@@ -333,10 +342,10 @@ struct Device {
   // kernel timing (events recorded around launches while ctx timing is on)
   const bool* timing = nullptr;
   const std::atomic<uint64_t>* wave_max = nullptr;  // the context's latency-path threshold
-  static constexpr int kKernels = 5;  // PBFTV_K_*
+  static constexpr int kKernels = 6;  // PBFTV_K_*
   std::vector<std::pair<hipEvent_t, hipEvent_t>> pending[kKernels];
-  double acc_ms[kKernels] = {0, 0, 0, 0, 0};
-  uint64_t launches[kKernels] = {0, 0, 0, 0, 0};
+  double acc_ms[kKernels] = {0, 0, 0, 0, 0, 0};
+  uint64_t launches[kKernels] = {0, 0, 0, 0, 0, 0};
 };
 
 // key-order scratch: a fresh allocation gets its header zeroed (the sort's
@@ -1284,6 +1293,8 @@ void pbftv_close(pbftv_ctx* ctx) {
     for (auto& b : d->tab_scratch) b.release();
     d->tab_keys.release();
     d->gtab.reset();
+    d->vb_gtab.reset();
+    d->vb_pub.release();
     d->vs.release();
     for (DevBuf* b : {&d->qptrs, &d->key_valid, &d->hashes, &d->sigs, &d->key_idx,
                       &d->bitmap, &d->data, &d->offsets, &d->lengths, &d->order,
@@ -1863,6 +1874,37 @@ static int for_each_device(pbftv_ctx* ctx, Fn fn) {
 }
 }  // extern "C++"
 
+// The G table of width wg on d's GPU: once per GPU and width while any context
+// holds it (g_tables), built here if nobody does.  d.mu is held.
+static int acquire_g_table(Device& d, int wg, std::shared_ptr<DevBuf>* out,
+                           std::chrono::steady_clock::time_point& t0) {
+  std::shared_ptr<std::mutex> build_mu;
+  {
+    std::lock_guard<std::mutex> gl(g_tables_mu);
+    build_mu = g_tables[{d.id, wg}].build;
+  }
+  std::lock_guard<std::mutex> bl(*build_mu);  // one builder per (GPU, width); others wait here, not globally
+  {
+    std::lock_guard<std::mutex> gl(g_tables_mu);
+    *out = g_tables[{d.id, wg}].tab.lock();
+  }
+  if (*out) return PBFTV_OK;
+  auto t = std::make_shared<DevBuf>();
+  HIP_TRY(t->ensure(pbftv::table_bytes(wg)));
+  DevBuf dummy;
+  HIP_TRY(dummy.ensure(64));
+  trace("G table allocation", d.id, t0);
+  const int r = build_tables(d, wg, nullptr, 0, 1, 1, dummy.as<uint32_t>(), {t->p});
+  if (r != PBFTV_OK) return r;
+  trace("G table build", d.id, t0);
+  {
+    std::lock_guard<std::mutex> gl(g_tables_mu);
+    g_tables[{d.id, wg}].tab = t;
+  }
+  *out = std::move(t);
+  return PBFTV_OK;
+}
+
 // One attempt at a device's tables: geometry from the HBM free now, then the G
 // table (shared per GPU and width) and the key tables (pbftv_register_keys).
 static int register_tables(Device& d, const std::vector<uint32_t>& le, uint32_t k, uint32_t* valid,
@@ -1888,31 +1930,8 @@ static int register_tables(Device& d, const std::vector<uint32_t>& le, uint32_t 
   if (d.gbits != wg || !d.gtab) {  // G table: once per GPU and width while any context holds it
     d.gtab.reset();
     d.gbits = 0;
-    std::shared_ptr<std::mutex> build_mu;
-    {
-      std::lock_guard<std::mutex> gl(g_tables_mu);
-      build_mu = g_tables[{d.id, wg}].build;
-    }
-    std::lock_guard<std::mutex> bl(*build_mu);  // one builder per (GPU, width); others wait here, not globally
-    {
-      std::lock_guard<std::mutex> gl(g_tables_mu);
-      d.gtab = g_tables[{d.id, wg}].tab.lock();
-    }
-    if (!d.gtab) {
-      auto t = std::make_shared<DevBuf>();
-      HIP_TRY(t->ensure(pbftv::table_bytes(wg)));
-      DevBuf dummy;
-      HIP_TRY(dummy.ensure(64));
-      trace("G table allocation", d.id, t0);
-      const int r = build_tables(d, wg, nullptr, 0, 1, 1, dummy.as<uint32_t>(), {t->p});
-      if (r != PBFTV_OK) return r;
-      trace("G table build", d.id, t0);
-      {
-        std::lock_guard<std::mutex> gl(g_tables_mu);
-        g_tables[{d.id, wg}].tab = t;
-      }
-      d.gtab = std::move(t);
-    }
+    const int r = acquire_g_table(d, wg, &d.gtab, t0);
+    if (r != PBFTV_OK) return r;
     d.gbits = wg;
   }
   d.qbits = wq;
@@ -2226,6 +2245,91 @@ int pbftv_ecdsa_p256_verify_batch_dev(pbftv_ctx* ctx, int dev, const uint8_t* d_
   std::lock_guard<std::mutex> lk(d.mu);
   HIP_TRY(hipSetDevice(d.id));
   return verify_on_device(d, d_hashes, d_sig_rs, d_key_idx, n, d_bitmap, pick_stream(d, stream));
+}
+
+// ---- verify under keys that were never registered (varbase.h) ----
+// One batch on stream st: the keys checked (k_varbase_keys), the unchanged
+// stage 1 in arrival order with "key i of n" for signature i, then k_varbase
+// against the width-16 G table.  Scratch and its ordering across streams as
+// in verify_on_device, so the context's quiesce and the deferred frees count
+// this work like any other *_dev verify.  Reads nothing of the registered key
+// set.  d.mu is held.
+static int varbase_on_device(Device& d, const uint8_t* d_hashes, const uint8_t* d_sigs, const uint8_t* d_pub,
+                             uint64_t n, uint8_t* d_bitmap, hipStream_t st) {
+  if (n == 0) return PBFTV_OK;
+  if (!d.vb_gtab) {  // first use: the G table from the per-GPU cache (built if no context holds it)
+    auto t0 = std::chrono::steady_clock::now();
+    const int r = acquire_g_table(d, pbftv::kVarbaseGBits, &d.vb_gtab, t0);
+    if (r != PBFTV_OK) return r;
+    HIP_TRY(hipDeviceGetAttribute(&d.vb_cus, hipDeviceAttributeMultiprocessorCount, d.id));
+  }
+  VerifyScratch* own = nullptr;
+  auto it = d.stream_scratch.find(st);
+  if (it != d.stream_scratch.end()) own = it->second.get();
+  VerifyScratch& sc = own ? *own : d.vs;
+  note_busy(d, n, 19.0);  // (~19 ns per signature at 1M)
+  const uint64_t lanes = std::min<uint64_t>(pbftv::varbase_lanes(d.vb_cus), (n + 255) / 256 * 256);
+  HIP_TRY(sc.rec.ensure(pbftv::ecdsa_record_bytes(n)));
+  HIP_TRY(sc.prefix.ensure(pbftv::scalar_prefix_bytes(n)));
+  HIP_TRY(sc.vb_aux.ensure(pbftv::varbase_aux_bytes(n)));
+  HIP_TRY(sc.vb_tab.ensure(pbftv::varbase_table_bytes(lanes)));
+  if (!own) HIP_TRY(scratch_acquire(d, st));
+  HIP_TRY(pbftv::launch_varbase_keys(d_pub, n, sc.vb_aux.p, st));
+  HIP_TRY(timed(d, PBFTV_K_ECDSA_SCALARS, st, [&] {
+    return pbftv::launch_ecdsa_scalars(d_hashes, d_sigs, pbftv::varbase_index(sc.vb_aux.p, n), n,
+                                       pbftv::varbase_valid(sc.vb_aux.p, n), (uint32_t)n, sc.rec.p, sc.prefix.p,
+                                       pbftv::KeyOrder{nullptr, nullptr, 0}, st);
+  }));
+  HIP_TRY(timed(d, PBFTV_K_ECDSA_VARBASE, st, [&] {
+    return pbftv::launch_varbase(sc.rec.p, sc.vb_aux.p, n, d.vb_gtab->as<uint32_t>(), sc.vb_tab.p, lanes, d_bitmap,
+                                 st);
+  }));
+  if (!own) HIP_TRY(scratch_release(d, st));
+  return PBFTV_OK;
+}
+
+int pbftv_ecdsa_p256_verify_pubkey_batch_dev(pbftv_ctx* ctx, int dev, const uint8_t* d_hashes,
+                                             const uint8_t* d_sig_rs, const uint8_t* d_pub_xy, uint64_t n,
+                                             uint8_t* d_bitmap, void* stream) {
+  if (!ctx || dev < 0 || dev >= (int)ctx->devs.size()) return fail(PBFTV_EINVAL, "bad context or device index");
+  if (n >> 32) return fail(PBFTV_EINVAL, "n must be below 2^32");
+  if (n == 0) return PBFTV_OK;
+  if (!d_hashes || !d_sig_rs || !d_pub_xy || !d_bitmap) return fail(PBFTV_EINVAL, "null buffer");
+  if (((uintptr_t)d_hashes | (uintptr_t)d_sig_rs | (uintptr_t)d_pub_xy) & 15u)
+    return fail(PBFTV_EINVAL, "hashes/sigs/keys must be 16-B aligned");
+  Device& d = *ctx->devs[dev];
+  std::lock_guard<std::mutex> lk(d.mu);
+  HIP_TRY(hipSetDevice(d.id));
+  return varbase_on_device(d, d_hashes, d_sig_rs, d_pub_xy, n, d_bitmap, pick_stream(d, stream));
+}
+
+// Host form: contiguous shards over the context's devices; each copies its
+// shard in, runs the device form on its stream and copies its bitmap back (no
+// chunk overlap: the kernel time is ~10x the copies').
+int pbftv_ecdsa_p256_verify_pubkey_batch(pbftv_ctx* ctx, const uint8_t* hashes, const uint8_t* sig_rs,
+                                         const uint8_t* pub_xy, uint64_t n, uint8_t* out_bitmap) {
+  if (!ctx) return fail(PBFTV_EINVAL, "ctx is null");
+  if (n >> 32) return fail(PBFTV_EINVAL, "n must be below 2^32");
+  if (n == 0) return PBFTV_OK;
+  if (!hashes || !sig_rs || !pub_xy || !out_bitmap) return fail(PBFTV_EINVAL, "null buffer");
+  return run_sharded(ctx, n, [&](Device& d, Shard s) -> int {
+    std::lock_guard<std::mutex> lk(d.mu);
+    HIP_TRY(hipSetDevice(d.id));
+    const uint64_t m = s.hi - s.lo;
+    HIP_TRY(d.hashes.ensure(32 * m + 64));
+    HIP_TRY(d.sigs.ensure(64 * m + 64));
+    HIP_TRY(d.vb_pub.ensure(64 * m + 64));
+    HIP_TRY(d.bitmap.ensure((m + 7) / 8 + 8));
+    HIP_TRY(hipMemcpyAsync(d.hashes.p, hashes + 32 * s.lo, 32 * m, hipMemcpyHostToDevice, d.stream));
+    HIP_TRY(hipMemcpyAsync(d.sigs.p, sig_rs + 64 * s.lo, 64 * m, hipMemcpyHostToDevice, d.stream));
+    HIP_TRY(hipMemcpyAsync(d.vb_pub.p, pub_xy + 64 * s.lo, 64 * m, hipMemcpyHostToDevice, d.stream));
+    const int rc = varbase_on_device(d, d.hashes.as<uint8_t>(), d.sigs.as<uint8_t>(), d.vb_pub.as<uint8_t>(), m,
+                                     d.bitmap.as<uint8_t>(), d.stream);
+    if (rc != PBFTV_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(out_bitmap + s.lo / 8, d.bitmap.p, (m + 7) / 8, hipMemcpyDeviceToHost, d.stream));
+    HIP_TRY(hipStreamSynchronize(d.stream));
+    return PBFTV_OK;
+  });
 }
 
 int pbftv_ecdsa_p256_verify_batch(pbftv_ctx* ctx, const uint8_t* hashes, const uint8_t* sig_rs,

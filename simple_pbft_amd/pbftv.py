@@ -135,6 +135,9 @@ def lib() -> ctypes.CDLL:
         "pbftv_ecdsa_p256_verify_batch": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_uint64, _vp]),
         "pbftv_ecdsa_p256_verify_batch_dev": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, _vp, ctypes.c_uint64, _vp,
                                                              _vp]),
+        "pbftv_ecdsa_p256_verify_pubkey_batch": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_uint64, _vp]),
+        "pbftv_ecdsa_p256_verify_pubkey_batch_dev": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, _vp,
+                                                                    ctypes.c_uint64, _vp, _vp]),
         "pbftv_qc_verify": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_uint64, ctypes.c_uint32, _vp,
                                            ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_int)]),
     }
@@ -816,6 +819,24 @@ class Verifier:
         self._sync_env()
         _check(self._L.pbftv_ecdsa_p256_verify_batch_dev(self._h, dev, d_hashes, d_sigs, d_key_idx, n, d_bitmap,
                                                          stream))
+
+    def verify_pubkey_batch(self, hashes: np.ndarray, sig_rs: np.ndarray, pub_xy: np.ndarray) -> np.ndarray:
+        """pbftv_ecdsa_p256_verify_pubkey_batch: signature i under its own key
+        pub_xy[i] (X||Y big-endian); no registered keys needed or touched."""
+        hashes = np.ascontiguousarray(hashes, np.uint8).reshape(-1, 32)
+        sig_rs = np.ascontiguousarray(sig_rs, np.uint8).reshape(-1, 64)
+        pub_xy = np.ascontiguousarray(pub_xy, np.uint8).reshape(-1, 64)
+        n = hashes.shape[0]
+        assert sig_rs.shape[0] == n and pub_xy.shape[0] == n
+        bm = np.zeros((n + 7) // 8 + 1, np.uint8)
+        _check(self._L.pbftv_ecdsa_p256_verify_pubkey_batch(self._h, hashes.ctypes.data, sig_rs.ctypes.data,
+                                                            pub_xy.ctypes.data, n, bm.ctypes.data))
+        return bitmap_to_bool(bm, n)
+
+    def verify_pubkey_batch_dev(self, dev: int, d_hashes: int, d_sigs: int, d_pub_xy: int, n: int, d_bitmap: int,
+                                stream: int | None = None):
+        _check(self._L.pbftv_ecdsa_p256_verify_pubkey_batch_dev(self._h, dev, d_hashes, d_sigs, d_pub_xy, n,
+                                                                d_bitmap, stream))
 
     def sha256_order_dev(self, dev: int, d_lengths: int, n: int, d_order: int, stream: int | None = None):
         _check(self._L.pbftv_sha256_order_dev(self._h, dev, d_lengths, n, d_order, stream))
