@@ -119,6 +119,77 @@ func (x *Ctx) FlushRequests(reqs []RequestMsg, sigs [][64]byte, keyIdx []uint32,
 	return res, nil
 }
 
+// FlushRequestsWireKey is FlushRequests for clients that were never
+// registered: request i's key travels with it in keys (see KeyFormat), and
+// the call is still one GPU round trip.  No RegisterKeys call is needed and
+// the registered keys are not touched.  assigned may be nil.
+func (x *Ctx) FlushRequestsWireKey(reqs []RequestMsg, sigs [][64]byte, keys []byte, format KeyFormat,
+	assigned []int64) (RequestResult, error) {
+	n := len(reqs)
+	if len(sigs) != n || (assigned != nil && len(assigned) != n) {
+		return RequestResult{}, &Error{Code: EINVAL, Msg: "column lengths differ"}
+	}
+	kp, err := wireKeys(keys, format, n)
+	if err != nil {
+		return RequestResult{}, err
+	}
+	if n == 0 {
+		return RequestResult{}, nil
+	}
+	ts, seqs := make([]int64, n), make([]int64, n)
+	cids, ops := make([]string, n), make([]string, n)
+	for i, r := range reqs {
+		ts[i], seqs[i], cids[i], ops[i] = r.Timestamp, r.SequenceID, r.ClientID, r.Operation
+	}
+	cid, op := packStrings(cids), packStrings(ops)
+	res := RequestResult{Digests: make([][32]byte, n)}
+	var cons *C.uint8_t
+	if assigned != nil {
+		res.ConsensusDigests = make([][32]byte, n)
+		cons = digestPtr(res.ConsensusDigests)
+	}
+	sbm := make([]byte, (n+7)/8+1)
+	err = call(func() C.int { return C.pbftv_flush_requests_wirekey(x.c, C.uint64_t(n), i64(ts), u8(cid.blob), u64(cid.off), u32(cid.ln),
+		u8(op.blob), u64(op.off), u32(op.ln), i64(seqs), sigPtr(sigs), kp, C.int(format), i64(assigned),
+		digestPtr(res.Digests), u8(sbm), cons) })
+	if err != nil {
+		return RequestResult{}, err
+	}
+	res.SigOK = bits(sbm, n)
+	return res, nil
+}
+
+// FlushRepliesWireKey is FlushReplies with reply i's key carried in keys.
+func (x *Ctx) FlushRepliesWireKey(reps []ReplyMsg, sigs [][64]byte, keys []byte, format KeyFormat) ([][32]byte,
+	[]bool, error) {
+	n := len(reps)
+	if len(sigs) != n {
+		return nil, nil, &Error{Code: EINVAL, Msg: "column lengths differ"}
+	}
+	kp, err := wireKeys(keys, format, n)
+	if err != nil {
+		return nil, nil, err
+	}
+	if n == 0 {
+		return nil, nil, nil
+	}
+	views, ts := make([]int64, n), make([]int64, n)
+	cids, ids, results := make([]string, n), make([]string, n), make([]string, n)
+	for i, r := range reps {
+		views[i], ts[i], cids[i], ids[i], results[i] = r.ViewID, r.Timestamp, r.ClientID, r.NodeID, r.Result
+	}
+	cid, id, rs := packStrings(cids), packStrings(ids), packStrings(results)
+	dg := make([][32]byte, n)
+	sbm := make([]byte, (n+7)/8+1)
+	err = call(func() C.int { return C.pbftv_flush_replies_wirekey(x.c, C.uint64_t(n), i64(views), i64(ts), u8(cid.blob), u64(cid.off),
+		u32(cid.ln), u8(id.blob), u64(id.off), u32(id.ln), u8(rs.blob), u64(rs.off), u32(rs.ln), sigPtr(sigs), kp,
+		C.int(format), digestPtr(dg), u8(sbm)) })
+	if err != nil {
+		return nil, nil, err
+	}
+	return dg, bits(sbm, n), nil
+}
+
 // FlushReplies checks the replicas' signatures on a snapshot of replies (the
 // client's reply collection; the reference never checks them, node.go:269-274).
 func (x *Ctx) FlushReplies(reps []ReplyMsg, sigs [][64]byte, keyIdx []uint32) ([][32]byte, []bool, error) {

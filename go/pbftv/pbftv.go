@@ -315,6 +315,57 @@ func (x *Ctx) VerifyPubkeyBatch(hashes [][32]byte, sigs [][64]byte, pubXY [][64]
 	return bits(bm, n), nil
 }
 
+// KeyFormat says how the keys of a *WireKey call are encoded: one format per
+// call, key i at keys[format.Bytes()*i:], packed.
+type KeyFormat int
+
+const (
+	KeyXY               KeyFormat = C.PBFTV_KEY_XY                // X||Y, 64 bytes
+	KeySEC1Compressed   KeyFormat = C.PBFTV_KEY_SEC1_COMPRESSED   // elliptic.MarshalCompressed, 33 bytes
+	KeySEC1Uncompressed KeyFormat = C.PBFTV_KEY_SEC1_UNCOMPRESSED // elliptic.Marshal, 65 bytes
+)
+
+// Bytes is the size of one key in the format (0 for an unknown format).
+func (f KeyFormat) Bytes() int { return int(C.pbftv_key_bytes(C.int(f))) }
+
+// wireKeys checks that keys holds n keys of the format and returns its base.
+func wireKeys(keys []byte, format KeyFormat, n int) (*C.uint8_t, error) {
+	b := format.Bytes()
+	if b == 0 {
+		return nil, &Error{Code: EINVAL, Msg: "unknown key format"}
+	}
+	if len(keys) != n*b {
+		return nil, &Error{Code: EINVAL, Msg: "keys must hold one key of the format per message"}
+	}
+	return u8(keys), nil
+}
+
+// VerifyWireKeyBatch is VerifyPubkeyBatch with the keys as they came off the
+// wire: elliptic.MarshalCompressed (KeySEC1Compressed) or elliptic.Marshal
+// (KeySEC1Uncompressed) output, or X||Y (KeyXY), packed back to back.  A key
+// that elliptic.UnmarshalCompressed / Unmarshal would refuse gives false, not
+// an error; the square root of a compressed key is taken on the GPU.
+func (x *Ctx) VerifyWireKeyBatch(hashes [][32]byte, sigs [][64]byte, keys []byte, format KeyFormat) ([]bool, error) {
+	n := len(hashes)
+	if len(sigs) != n {
+		return nil, &Error{Code: EINVAL, Msg: "hashes and sigs differ in length"}
+	}
+	kp, err := wireKeys(keys, format, n)
+	if err != nil {
+		return nil, err
+	}
+	if n == 0 {
+		return nil, nil
+	}
+	bm := make([]byte, (n+7)/8)
+	err = call(func() C.int { return C.pbftv_ecdsa_p256_verify_wirekey_batch(x.c, (*C.uint8_t)(unsafe.Pointer(&hashes[0])),
+		(*C.uint8_t)(unsafe.Pointer(&sigs[0])), kp, C.int(format), C.uint64_t(n), u8(bm)) })
+	if err != nil {
+		return nil, err
+	}
+	return bits(bm, n), nil
+}
+
 // QCVerify verifies one quorum certificate and counts it: reached =
 // accepted >= quorum (quorum = 2f reproduces prepared()/committed(),
 // pbft/consensus/pbft_impl.go:207-232; 2f+1 checks a PBFT certificate).

@@ -490,6 +490,54 @@ int pbftv_ecdsa_p256_verify_pubkey_batch_dev(pbftv_ctx* ctx, int dev, const uint
                                              const uint8_t* d_sig_rs, const uint8_t* d_pub_xy, uint64_t n,
                                              uint8_t* d_bitmap, void* stream);
 
+/* The same with the keys as they travel: one format per call, key i at
+ * keys + pbftv_key_bytes(key_format) * i (packed, no padding between keys).
+ * The SEC1 forms are what Go's elliptic.Marshal (uncompressed) and
+ * elliptic.MarshalCompressed write, decoded by the rules of SEC1 2.3.3/2.3.4
+ * as go1.19 elliptic.Unmarshal / UnmarshalCompressed apply them:
+ *   uncompressed  byte 0 must be 04 (the hybrid forms 06/07, 00 and every
+ *                 other value are rejected), 0 <= X, Y < p, point on the curve;
+ *   compressed    byte 0 must be 02 or 03, X < p, y = sqrt(X^3 - 3X + b) must
+ *                 exist (about half of all X have no point), and of the two
+ *                 roots the one with y mod 2 == byte 0 mod 2 is the key.
+ * The square root is taken on the device (one per key; +5.6 % on the verify
+ * step).  A key that fails decoding is a 0 bit, never an
+ * error.  PBFTV_KEY_XY is pbftv_ecdsa_p256_verify_pubkey_batch's pub_xy.
+ * Everything else -- semantics, bitmap, n = 0, n >= 2^32, no registered keys
+ * needed or touched, the _dev form's 16-B aligned base pointers and stream --
+ * is as stated above; an unknown key_format is PBFTV_EINVAL. */
+#define PBFTV_KEY_XY                0  /* X||Y, 64 B                          */
+#define PBFTV_KEY_SEC1_COMPRESSED   1  /* 02|03 || X, 33 B                    */
+#define PBFTV_KEY_SEC1_UNCOMPRESSED 2  /* 04 || X || Y, 65 B                  */
+uint32_t pbftv_key_bytes(int key_format);   /* 64 / 33 / 65; 0 = unknown     */
+int pbftv_ecdsa_p256_verify_wirekey_batch(pbftv_ctx* ctx, const uint8_t* hashes, const uint8_t* sig_rs,
+                                          const uint8_t* keys, int key_format, uint64_t n, uint8_t* out_bitmap);
+int pbftv_ecdsa_p256_verify_wirekey_batch_dev(pbftv_ctx* ctx, int dev, const uint8_t* d_hashes,
+                                              const uint8_t* d_sig_rs, const uint8_t* d_keys, int key_format,
+                                              uint64_t n, uint8_t* d_bitmap, void* stream);
+
+/* Flushes of client-signed messages: pbftv_flush_requests / pbftv_flush_replies
+ * with the signer's key carried per message (keys, key_format: as above) in
+ * place of key_idx, still one GPU round trip per device -- the digests never
+ * leave the device between the hash and the signature stage:
+ *   sig bit i = ecdsa.Verify(decode(key i), h_i, r_i, s_i)      -> out_sig_bitmap
+ * (a signature bitmap needs sig_rs and keys; n >= 2^32 with a bitmap wanted is
+ * PBFTV_EINVAL).  They need no registered keys (no PBFTV_ENOKEYS) and read and
+ * disturb nothing of the registered set.  Every other column and output is
+ * that of the registered form. */
+int pbftv_flush_requests_wirekey(pbftv_ctx* ctx, uint64_t n, const int64_t* timestamps, const uint8_t* client_ids,
+                                 const uint64_t* client_id_off, const uint32_t* client_id_len,
+                                 const uint8_t* operations, const uint64_t* operation_off,
+                                 const uint32_t* operation_len, const int64_t* sequence_ids, const uint8_t* sig_rs,
+                                 const uint8_t* keys, int key_format, const int64_t* assigned_seqs,
+                                 uint8_t* out_digests, uint8_t* out_sig_bitmap, uint8_t* out_consensus_digests);
+int pbftv_flush_replies_wirekey(pbftv_ctx* ctx, uint64_t n, const int64_t* view_ids, const int64_t* timestamps,
+                                const uint8_t* client_ids, const uint64_t* client_id_off,
+                                const uint32_t* client_id_len, const uint8_t* node_ids, const uint64_t* node_id_off,
+                                const uint32_t* node_id_len, const uint8_t* results, const uint64_t* result_off,
+                                const uint32_t* result_len, const uint8_t* sig_rs, const uint8_t* keys,
+                                int key_format, uint8_t* out_digests, uint8_t* out_sig_bitmap);
+
 /* Quorum certificate: verify n signatures and count acceptances.
  * *out_accepted = popcount; *out_quorum = (*out_accepted >= quorum).  With
  * quorum = 2f this is the reference's prepared()/committed() count

@@ -188,8 +188,11 @@ struct ArmArgs {
 hipError_t launch_ecdsa_wave_armed(int wg, int wq, const ArmArgs& a, hipStream_t st);
 
 // ---- ECDSA-P256 under unregistered keys (p256_varbase.hip, varbase.h) ----
-// Every signature carries its key (pub_xy: X||Y big-endian, 64 B each, 16-B
-// aligned).  launch_varbase_keys checks the keys into aux (varbase_aux_bytes:
+// Every signature carries its key: a column of varbase_key_bytes(key_format)
+// bytes each (0: unknown format), 16-B aligned, in one of include/pbftv.h's
+// PBFTV_KEY_* formats -- X||Y big-endian (64 B), or SEC1 compressed (33 B) /
+// uncompressed (65 B), decoded by sec1.h.  launch_varbase_keys checks the
+// keys into aux (varbase_aux_bytes:
 // validity words, identity indices -- what launch_ecdsa_scalars takes as
 // key_valid / key_idx with nkeys = n, arrival order -- and the keys in
 // Montgomery form); launch_varbase then verifies the stage-1 records against
@@ -202,7 +205,9 @@ const uint32_t* varbase_valid(const void* aux, uint64_t n);
 const uint32_t* varbase_index(const void* aux, uint64_t n);
 uint64_t varbase_lanes(int cus);
 size_t varbase_table_bytes(uint64_t lanes);
-hipError_t launch_varbase_keys(const uint8_t* pub_xy, uint64_t n, void* aux, hipStream_t st);
+constexpr int kVarbaseKeyXY = 0, kVarbaseKeySec1Compressed = 1, kVarbaseKeySec1Uncompressed = 2;  // = PBFTV_KEY_*
+uint32_t varbase_key_bytes(int key_format);
+hipError_t launch_varbase_keys(const uint8_t* keys, int key_format, uint64_t n, void* aux, hipStream_t st);
 hipError_t launch_varbase(const void* rec, const void* aux, uint64_t n, const uint32_t* gtab, void* tab,
                           uint64_t lanes, uint8_t* bitmap, hipStream_t st);
 

@@ -3,6 +3,10 @@
 //   k_varbase_keys  key_check per signature: validity word, identity index
 //                   (so the unchanged stage 1, k_ecdsa_scalars, treats lane i's
 //                   key as "key i of n"), the key left in Montgomery form.
+//   k_varbase_keys_sec1<FMT>  the same for keys in SEC1 wire form (sec1.h:
+//                   33 B compressed -- a square root mod p per key -- or 65 B
+//                   uncompressed), staged through LDS because a 33- or 65-byte
+//                   stride is not word aligned.
 //   k_varbase       one signature per lane, grid-stride: the lane's table
 //                   1Q .. 8Q in global scratch, the 4-bit fixed-window ladder
 //                   for u2*Q, 17 mixed additions of the width-16 G comb for
@@ -15,6 +19,7 @@
 #include <cstdlib>
 
 #include "kernels.h"
+#include "sec1.h"
 #include "varbase.h"
 #include "verify_kernels.h"
 
@@ -43,6 +48,49 @@ __global__ void __launch_bounds__(256) k_varbase_keys(const uint8_t* __restrict_
   fe xm, ym;
   const bool ok = key_check(xw, yw, xm, ym);
   if (!ok) {  // a harmless point (never used: valid = 0 makes stage 1 reject the signature)
+    fe_set(xm, kGxMont);
+    fe_set(ym, kGyMont);
+  }
+  valid[i] = ok ? 1u : 0u;
+  idx[i] = (uint32_t)i;
+  PBFTV_UNROLL for (int l = 0; l < 9; ++l) {
+    keys[(uint64_t)l * n + i] = xm.v[l];
+    keys[(uint64_t)(9 + l) * n + i] = ym.v[l];
+  }
+}
+
+// Keys in SEC1 wire form, one per lane, same outputs as k_varbase_keys.  A
+// block's 256 keys are one contiguous span that starts on a word boundary
+// (256 * stride is a multiple of 4 and the column is 16-B aligned): the block
+// copies it to LDS with coalesced word loads -- the ragged tail of the column's
+// last word byte by byte, so nothing past the last key is read -- and each
+// lane decodes its key from there.
+template <int FMT>
+__global__ void __launch_bounds__(256) k_varbase_keys_sec1(const uint8_t* __restrict__ wire, uint64_t n,
+                                                           uint32_t* __restrict__ valid, uint32_t* __restrict__ idx,
+                                                           uint32_t* __restrict__ keys) {
+  static_assert(FMT == kKeySec1Compressed || FMT == kKeySec1Uncompressed, "a SEC1 format");
+  constexpr uint32_t kStride = FMT == kKeySec1Compressed ? 33 : 65;
+  __shared__ uint32_t stage[kStride * 256 / 4];
+  const uint64_t first = (uint64_t)blockIdx.x * 256;  // (< n: the grid is ceil(n / 256) blocks)
+  const uint32_t cnt = (uint32_t)(n - first < 256 ? n - first : 256);
+  const uint32_t bytes = cnt * kStride;
+  const uint8_t* src = wire + first * kStride;
+  for (uint32_t w = threadIdx.x; 4 * w < bytes; w += 256) {
+    uint32_t v = 0;
+    if (4 * w + 4 <= bytes) {
+      v = *reinterpret_cast<const uint32_t*>(src + 4 * w);
+    } else {
+      for (uint32_t k = 0; 4 * w + k < bytes; ++k) v |= (uint32_t)src[4 * w + k] << (8 * k);
+    }
+    stage[w] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x >= cnt) return;
+  const uint64_t i = first + threadIdx.x;
+  fe xm, ym;
+  const bool ok = sec1_key_check(reinterpret_cast<const uint8_t*>(stage) + threadIdx.x * kStride, FMT, xm, ym);
+  if (!ok) {  // (as k_varbase_keys: G stands in, valid = 0 rejects the signature)
     fe_set(xm, kGxMont);
     fe_set(ym, kGyMont);
   }
@@ -170,11 +218,27 @@ uint64_t varbase_lanes(int cus) {
 
 size_t varbase_table_bytes(uint64_t lanes) { return (size_t)lanes * kVbLaneWords * 4; }
 
-hipError_t launch_varbase_keys(const uint8_t* pub_xy, uint64_t n, void* aux, hipStream_t st) {
+static_assert(kVarbaseKeyXY == kKeyXY && kVarbaseKeySec1Compressed == kKeySec1Compressed &&
+                  kVarbaseKeySec1Uncompressed == kKeySec1Uncompressed,
+              "kernels.h and sec1.h name the key formats alike");
+
+uint32_t varbase_key_bytes(int key_format) { return sec1_key_bytes(key_format); }
+
+hipError_t launch_varbase_keys(const uint8_t* keys, int key_format, uint64_t n, void* aux, hipStream_t st) {
   if (n == 0) return hipSuccess;
   uint32_t* w = reinterpret_cast<uint32_t*>(aux);
-  hipLaunchKernelGGL(k_varbase_keys, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, pub_xy, n, w, w + n,
-                     w + 2 * n);
+  const dim3 grid((uint32_t)((n + 255) / 256)), block(256);
+  if (key_format == kKeyXY) {
+    hipLaunchKernelGGL(k_varbase_keys, grid, block, 0, st, keys, n, w, w + n, w + 2 * n);
+  } else if ((uintptr_t)keys & 3u) {  // the SEC1 kernels load the column by words
+    return hipErrorInvalidValue;
+  } else if (key_format == kKeySec1Compressed) {
+    hipLaunchKernelGGL(k_varbase_keys_sec1<kKeySec1Compressed>, grid, block, 0, st, keys, n, w, w + n, w + 2 * n);
+  } else if (key_format == kKeySec1Uncompressed) {
+    hipLaunchKernelGGL(k_varbase_keys_sec1<kKeySec1Uncompressed>, grid, block, 0, st, keys, n, w, w + n, w + 2 * n);
+  } else {
+    return hipErrorInvalidValue;
+  }
   return hipGetLastError();
 }
 

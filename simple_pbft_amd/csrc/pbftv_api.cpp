@@ -2248,14 +2248,21 @@ int pbftv_ecdsa_p256_verify_batch_dev(pbftv_ctx* ctx, int dev, const uint8_t* d_
 }
 
 // ---- verify under keys that were never registered (varbase.h) ----
-// One batch on stream st: the keys checked (k_varbase_keys), the unchanged
+static_assert(PBFTV_KEY_XY == pbftv::kVarbaseKeyXY && PBFTV_KEY_SEC1_COMPRESSED == pbftv::kVarbaseKeySec1Compressed &&
+                  PBFTV_KEY_SEC1_UNCOMPRESSED == pbftv::kVarbaseKeySec1Uncompressed,
+              "include/pbftv.h and kernels.h name the key formats alike");
+
+uint32_t pbftv_key_bytes(int key_format) { return pbftv::varbase_key_bytes(key_format); }
+
+// One batch on stream st: the keys (d_keys: a column in key_format, PBFTV_KEY_*)
+// checked or decoded (k_varbase_keys / k_varbase_keys_sec1), the unchanged
 // stage 1 in arrival order with "key i of n" for signature i, then k_varbase
 // against the width-16 G table.  Scratch and its ordering across streams as
 // in verify_on_device, so the context's quiesce and the deferred frees count
 // this work like any other *_dev verify.  Reads nothing of the registered key
 // set.  d.mu is held.
-static int varbase_on_device(Device& d, const uint8_t* d_hashes, const uint8_t* d_sigs, const uint8_t* d_pub,
-                             uint64_t n, uint8_t* d_bitmap, hipStream_t st) {
+static int varbase_on_device(Device& d, const uint8_t* d_hashes, const uint8_t* d_sigs, const uint8_t* d_keys,
+                             int key_format, uint64_t n, uint8_t* d_bitmap, hipStream_t st) {
   if (n == 0) return PBFTV_OK;
   if (!d.vb_gtab) {  // first use: the G table from the per-GPU cache (built if no context holds it)
     auto t0 = std::chrono::steady_clock::now();
@@ -2274,7 +2281,7 @@ static int varbase_on_device(Device& d, const uint8_t* d_hashes, const uint8_t* 
   HIP_TRY(sc.vb_aux.ensure(pbftv::varbase_aux_bytes(n)));
   HIP_TRY(sc.vb_tab.ensure(pbftv::varbase_table_bytes(lanes)));
   if (!own) HIP_TRY(scratch_acquire(d, st));
-  HIP_TRY(pbftv::launch_varbase_keys(d_pub, n, sc.vb_aux.p, st));
+  HIP_TRY(pbftv::launch_varbase_keys(d_keys, key_format, n, sc.vb_aux.p, st));
   HIP_TRY(timed(d, PBFTV_K_ECDSA_SCALARS, st, [&] {
     return pbftv::launch_ecdsa_scalars(d_hashes, d_sigs, pbftv::varbase_index(sc.vb_aux.p, n), n,
                                        pbftv::varbase_valid(sc.vb_aux.p, n), (uint32_t)n, sc.rec.p, sc.prefix.p,
@@ -2288,48 +2295,64 @@ static int varbase_on_device(Device& d, const uint8_t* d_hashes, const uint8_t* 
   return PBFTV_OK;
 }
 
-int pbftv_ecdsa_p256_verify_pubkey_batch_dev(pbftv_ctx* ctx, int dev, const uint8_t* d_hashes,
-                                             const uint8_t* d_sig_rs, const uint8_t* d_pub_xy, uint64_t n,
-                                             uint8_t* d_bitmap, void* stream) {
+int pbftv_ecdsa_p256_verify_wirekey_batch_dev(pbftv_ctx* ctx, int dev, const uint8_t* d_hashes,
+                                              const uint8_t* d_sig_rs, const uint8_t* d_keys, int key_format,
+                                              uint64_t n, uint8_t* d_bitmap, void* stream) {
   if (!ctx || dev < 0 || dev >= (int)ctx->devs.size()) return fail(PBFTV_EINVAL, "bad context or device index");
+  if (!pbftv_key_bytes(key_format)) return fail(PBFTV_EINVAL, "unknown key format");
   if (n >> 32) return fail(PBFTV_EINVAL, "n must be below 2^32");
   if (n == 0) return PBFTV_OK;
-  if (!d_hashes || !d_sig_rs || !d_pub_xy || !d_bitmap) return fail(PBFTV_EINVAL, "null buffer");
-  if (((uintptr_t)d_hashes | (uintptr_t)d_sig_rs | (uintptr_t)d_pub_xy) & 15u)
+  if (!d_hashes || !d_sig_rs || !d_keys || !d_bitmap) return fail(PBFTV_EINVAL, "null buffer");
+  if (((uintptr_t)d_hashes | (uintptr_t)d_sig_rs | (uintptr_t)d_keys) & 15u)
     return fail(PBFTV_EINVAL, "hashes/sigs/keys must be 16-B aligned");
   Device& d = *ctx->devs[dev];
   std::lock_guard<std::mutex> lk(d.mu);
   HIP_TRY(hipSetDevice(d.id));
-  return varbase_on_device(d, d_hashes, d_sig_rs, d_pub_xy, n, d_bitmap, pick_stream(d, stream));
+  return varbase_on_device(d, d_hashes, d_sig_rs, d_keys, key_format, n, d_bitmap, pick_stream(d, stream));
+}
+
+int pbftv_ecdsa_p256_verify_pubkey_batch_dev(pbftv_ctx* ctx, int dev, const uint8_t* d_hashes,
+                                             const uint8_t* d_sig_rs, const uint8_t* d_pub_xy, uint64_t n,
+                                             uint8_t* d_bitmap, void* stream) {
+  return pbftv_ecdsa_p256_verify_wirekey_batch_dev(ctx, dev, d_hashes, d_sig_rs, d_pub_xy, PBFTV_KEY_XY, n, d_bitmap,
+                                                   stream);
 }
 
 // Host form: contiguous shards over the context's devices; each copies its
-// shard in, runs the device form on its stream and copies its bitmap back (no
+// shard in (the keys from stride * s.lo, to the start of its own aligned
+// buffer), runs the device form on its stream and copies its bitmap back (no
 // chunk overlap: the kernel time is ~10x the copies').
-int pbftv_ecdsa_p256_verify_pubkey_batch(pbftv_ctx* ctx, const uint8_t* hashes, const uint8_t* sig_rs,
-                                         const uint8_t* pub_xy, uint64_t n, uint8_t* out_bitmap) {
+int pbftv_ecdsa_p256_verify_wirekey_batch(pbftv_ctx* ctx, const uint8_t* hashes, const uint8_t* sig_rs,
+                                          const uint8_t* keys, int key_format, uint64_t n, uint8_t* out_bitmap) {
   if (!ctx) return fail(PBFTV_EINVAL, "ctx is null");
+  const uint64_t stride = pbftv_key_bytes(key_format);
+  if (!stride) return fail(PBFTV_EINVAL, "unknown key format");
   if (n >> 32) return fail(PBFTV_EINVAL, "n must be below 2^32");
   if (n == 0) return PBFTV_OK;
-  if (!hashes || !sig_rs || !pub_xy || !out_bitmap) return fail(PBFTV_EINVAL, "null buffer");
+  if (!hashes || !sig_rs || !keys || !out_bitmap) return fail(PBFTV_EINVAL, "null buffer");
   return run_sharded(ctx, n, [&](Device& d, Shard s) -> int {
     std::lock_guard<std::mutex> lk(d.mu);
     HIP_TRY(hipSetDevice(d.id));
     const uint64_t m = s.hi - s.lo;
     HIP_TRY(d.hashes.ensure(32 * m + 64));
     HIP_TRY(d.sigs.ensure(64 * m + 64));
-    HIP_TRY(d.vb_pub.ensure(64 * m + 64));
+    HIP_TRY(d.vb_pub.ensure(stride * m + 64));
     HIP_TRY(d.bitmap.ensure((m + 7) / 8 + 8));
     HIP_TRY(hipMemcpyAsync(d.hashes.p, hashes + 32 * s.lo, 32 * m, hipMemcpyHostToDevice, d.stream));
     HIP_TRY(hipMemcpyAsync(d.sigs.p, sig_rs + 64 * s.lo, 64 * m, hipMemcpyHostToDevice, d.stream));
-    HIP_TRY(hipMemcpyAsync(d.vb_pub.p, pub_xy + 64 * s.lo, 64 * m, hipMemcpyHostToDevice, d.stream));
-    const int rc = varbase_on_device(d, d.hashes.as<uint8_t>(), d.sigs.as<uint8_t>(), d.vb_pub.as<uint8_t>(), m,
-                                     d.bitmap.as<uint8_t>(), d.stream);
+    HIP_TRY(hipMemcpyAsync(d.vb_pub.p, keys + stride * s.lo, stride * m, hipMemcpyHostToDevice, d.stream));
+    const int rc = varbase_on_device(d, d.hashes.as<uint8_t>(), d.sigs.as<uint8_t>(), d.vb_pub.as<uint8_t>(),
+                                     key_format, m, d.bitmap.as<uint8_t>(), d.stream);
     if (rc != PBFTV_OK) return rc;
     HIP_TRY(hipMemcpyAsync(out_bitmap + s.lo / 8, d.bitmap.p, (m + 7) / 8, hipMemcpyDeviceToHost, d.stream));
     HIP_TRY(hipStreamSynchronize(d.stream));
     return PBFTV_OK;
   });
+}
+
+int pbftv_ecdsa_p256_verify_pubkey_batch(pbftv_ctx* ctx, const uint8_t* hashes, const uint8_t* sig_rs,
+                                         const uint8_t* pub_xy, uint64_t n, uint8_t* out_bitmap) {
+  return pbftv_ecdsa_p256_verify_wirekey_batch(ctx, hashes, sig_rs, pub_xy, PBFTV_KEY_XY, n, out_bitmap);
 }
 
 int pbftv_ecdsa_p256_verify_batch(pbftv_ctx* ctx, const uint8_t* hashes, const uint8_t* sig_rs,
@@ -2866,18 +2889,58 @@ int pbftv_hash_hex(pbftv_ctx* ctx, const uint8_t* content, uint64_t len, char ou
 // k_sha256 hashes them, the signature stage runs on the digests in HBM, and
 // the results come back in one D2H copy.  The digest_*_batch functions are the
 // flushes with no signatures.
-int pbftv_flush_requests(pbftv_ctx* ctx, uint64_t n, const int64_t* timestamps, const uint8_t* client_ids,
-                         const uint64_t* client_id_off, const uint32_t* client_id_len, const uint8_t* operations,
-                         const uint64_t* operation_off, const uint32_t* operation_len, const int64_t* sequence_ids,
-                         const uint8_t* sig_rs, const uint32_t* key_idx, const int64_t* assigned_seqs,
-                         uint8_t* out_digests, uint8_t* out_sig_bitmap, uint8_t* out_consensus_digests) {
+// Who signed a flush's messages: registered keys named by index (key_idx), or
+// a key carried with every message (keys: a packed column in key_format, one
+// of PBFTV_KEY_*; the *_wirekey flushes).
+struct FlushSigner {
+  const uint32_t* key_idx;
+  const uint8_t* keys;
+  int key_format;
+  uint64_t stride;  // bytes per carried key; 0: registered keys
+  bool given() const { return stride ? keys != nullptr : key_idx != nullptr; }
+};
+
+static FlushSigner registered_signer(const uint32_t* key_idx) { return {key_idx, nullptr, 0, 0}; }
+
+// the argument checks the two kinds of signer differ in; PBFTV_OK: go on
+static int check_signer(const FlushSigner& by, uint64_t n, bool sig, const uint8_t* sig_rs) {
+  if (by.stride) {
+    if (n && sig && (!sig_rs || !by.given())) return fail(PBFTV_EINVAL, "signatures requested without sig_rs/keys");
+    if (sig && (n >> 32)) return fail(PBFTV_EINVAL, "n must be below 2^32");
+    return PBFTV_OK;
+  }
+  if (n && sig && (!sig_rs || !by.given())) return fail(PBFTV_EINVAL, "signatures requested without sig_rs/key_idx");
+  return PBFTV_OK;
+}
+
+// shard [lo, lo + m)'s signer column into the Packer; its arena offset
+static size_t add_signer(Packer& p, const FlushSigner& by, uint64_t lo, uint64_t m) {
+  return by.stride ? p.add(by.keys + by.stride * lo, by.stride * m) : p.add(by.key_idx + lo, 4 * m);
+}
+
+// the signature stage of a flush on the digests in HBM (d.mu held)
+static int flush_verify(Device& d, const FlushSigner& by, size_t o_sig, size_t o_key, uint64_t m) {
+  HIP_TRY(d.bitmap.ensure((m + 7) / 8 + 8));
+  if (by.stride)
+    return varbase_on_device(d, d.digests.as<uint8_t>(), at<uint8_t>(d, o_sig), at<uint8_t>(d, o_key), by.key_format,
+                             m, d.bitmap.as<uint8_t>(), d.stream);
+  return verify_on_device(d, d.digests.as<uint8_t>(), at<uint8_t>(d, o_sig), at<uint32_t>(d, o_key), m,
+                          d.bitmap.as<uint8_t>(), d.stream);
+}
+
+static int flush_requests_by(pbftv_ctx* ctx, uint64_t n, const int64_t* timestamps, const uint8_t* client_ids,
+                             const uint64_t* client_id_off, const uint32_t* client_id_len, const uint8_t* operations,
+                             const uint64_t* operation_off, const uint32_t* operation_len,
+                             const int64_t* sequence_ids, const uint8_t* sig_rs, const FlushSigner& by,
+                             const int64_t* assigned_seqs, uint8_t* out_digests, uint8_t* out_sig_bitmap,
+                             uint8_t* out_consensus_digests) {
   if (!ctx) return fail(PBFTV_EINVAL, "ctx is null");
   if (n && (!timestamps || !client_id_off || !client_id_len || !operation_off || !operation_len || !sequence_ids))
     return fail(PBFTV_EINVAL, "null buffer");
   const bool sig = out_sig_bitmap != nullptr, two = out_consensus_digests != nullptr;
-  if (n && sig && (!sig_rs || !key_idx)) return fail(PBFTV_EINVAL, "signatures requested without sig_rs/key_idx");
+  if (const int rc = check_signer(by, n, sig, sig_rs)) return rc;
   if (n && two && !assigned_seqs) return fail(PBFTV_EINVAL, "consensus digests requested without assigned_seqs");
-  if (sig && !keys_ready(ctx)) return fail(PBFTV_ENOKEYS, "pbftv_register_keys has not been called");
+  if (sig && !by.stride && !keys_ready(ctx)) return fail(PBFTV_ENOKEYS, "pbftv_register_keys has not been called");
   return run_sharded(ctx, n, [&](Device& d, Shard s) -> int {
     const uint64_t m = s.hi - s.lo;
     Packer p;
@@ -2890,7 +2953,7 @@ int pbftv_flush_requests(pbftv_ctx* ctx, uint64_t n, const int64_t* timestamps, 
     const size_t o_aseq = two ? p.add(assigned_seqs + s.lo, 8 * m) : 0;
     const auto cid = p.add_str(client_ids, client_id_off, client_id_len, s.lo, s.hi);
     const auto op = p.add_str(operations, operation_off, operation_len, s.lo, s.hi);
-    const size_t o_sig = sig ? p.add(sig_rs + 64 * s.lo, 64 * m) : 0, o_key = sig ? p.add(key_idx + s.lo, 4 * m) : 0;
+    const size_t o_sig = sig ? p.add(sig_rs + 64 * s.lo, 64 * m) : 0, o_key = sig ? add_signer(p, by, s.lo, m) : 0;
     std::lock_guard<std::mutex> lk(d.mu);
     HIP_TRY(hipSetDevice(d.id));
     int rc = upload(d, p);
@@ -2907,15 +2970,36 @@ int pbftv_flush_requests(pbftv_ctx* ctx, uint64_t n, const int64_t* timestamps, 
     });
     if (rc != PBFTV_OK) return rc;
     if (sig) {
-      HIP_TRY(d.bitmap.ensure((m + 7) / 8 + 8));
-      rc = verify_on_device(d, d.digests.as<uint8_t>(), at<uint8_t>(d, o_sig), at<uint32_t>(d, o_key), m,
-                            d.bitmap.as<uint8_t>(), d.stream);
+      rc = flush_verify(d, by, o_sig, o_key, m);
       if (rc != PBFTV_OK) return rc;
     }
     return results_out(d, s.lo, m, {{kDigests, d.digests.p, out_digests},
                                     {kDigests, d.digests.as<uint8_t>() + 32 * m, out_consensus_digests},
                                     {kBitmap, d.bitmap.p, sig ? out_sig_bitmap : nullptr}});
   });
+}
+
+int pbftv_flush_requests(pbftv_ctx* ctx, uint64_t n, const int64_t* timestamps, const uint8_t* client_ids,
+                         const uint64_t* client_id_off, const uint32_t* client_id_len, const uint8_t* operations,
+                         const uint64_t* operation_off, const uint32_t* operation_len, const int64_t* sequence_ids,
+                         const uint8_t* sig_rs, const uint32_t* key_idx, const int64_t* assigned_seqs,
+                         uint8_t* out_digests, uint8_t* out_sig_bitmap, uint8_t* out_consensus_digests) {
+  return flush_requests_by(ctx, n, timestamps, client_ids, client_id_off, client_id_len, operations, operation_off,
+                           operation_len, sequence_ids, sig_rs, registered_signer(key_idx), assigned_seqs,
+                           out_digests, out_sig_bitmap, out_consensus_digests);
+}
+
+int pbftv_flush_requests_wirekey(pbftv_ctx* ctx, uint64_t n, const int64_t* timestamps, const uint8_t* client_ids,
+                                 const uint64_t* client_id_off, const uint32_t* client_id_len,
+                                 const uint8_t* operations, const uint64_t* operation_off,
+                                 const uint32_t* operation_len, const int64_t* sequence_ids, const uint8_t* sig_rs,
+                                 const uint8_t* keys, int key_format, const int64_t* assigned_seqs,
+                                 uint8_t* out_digests, uint8_t* out_sig_bitmap, uint8_t* out_consensus_digests) {
+  const uint64_t stride = pbftv_key_bytes(key_format);
+  if (!stride) return fail(PBFTV_EINVAL, "unknown key format");
+  return flush_requests_by(ctx, n, timestamps, client_ids, client_id_off, client_id_len, operations, operation_off,
+                           operation_len, sequence_ids, sig_rs, FlushSigner{nullptr, keys, key_format, stride},
+                           assigned_seqs, out_digests, out_sig_bitmap, out_consensus_digests);
 }
 
 int pbftv_digest_request_batch(pbftv_ctx* ctx, uint64_t n, const int64_t* timestamps, const uint8_t* client_ids,
@@ -2937,19 +3021,19 @@ int pbftv_digest_vote_batch(pbftv_ctx* ctx, uint64_t n, const int64_t* view_ids,
                            out_digests, nullptr, nullptr);
 }
 
-int pbftv_flush_replies(pbftv_ctx* ctx, uint64_t n, const int64_t* view_ids, const int64_t* timestamps,
-                        const uint8_t* client_ids, const uint64_t* client_id_off, const uint32_t* client_id_len,
-                        const uint8_t* node_ids, const uint64_t* node_id_off, const uint32_t* node_id_len,
-                        const uint8_t* results, const uint64_t* result_off, const uint32_t* result_len,
-                        const uint8_t* sig_rs, const uint32_t* key_idx, uint8_t* out_digests,
-                        uint8_t* out_sig_bitmap) {
+static int flush_replies_by(pbftv_ctx* ctx, uint64_t n, const int64_t* view_ids, const int64_t* timestamps,
+                            const uint8_t* client_ids, const uint64_t* client_id_off, const uint32_t* client_id_len,
+                            const uint8_t* node_ids, const uint64_t* node_id_off, const uint32_t* node_id_len,
+                            const uint8_t* results, const uint64_t* result_off, const uint32_t* result_len,
+                            const uint8_t* sig_rs, const FlushSigner& by, uint8_t* out_digests,
+                            uint8_t* out_sig_bitmap) {
   if (!ctx) return fail(PBFTV_EINVAL, "ctx is null");
   if (n && (!view_ids || !timestamps || !client_id_off || !client_id_len || !node_id_off || !node_id_len ||
             !result_off || !result_len))
     return fail(PBFTV_EINVAL, "null buffer");
   const bool sig = out_sig_bitmap != nullptr;
-  if (n && sig && (!sig_rs || !key_idx)) return fail(PBFTV_EINVAL, "signatures requested without sig_rs/key_idx");
-  if (sig && !keys_ready(ctx)) return fail(PBFTV_ENOKEYS, "pbftv_register_keys has not been called");
+  if (const int rc = check_signer(by, n, sig, sig_rs)) return rc;
+  if (sig && !by.stride && !keys_ready(ctx)) return fail(PBFTV_ENOKEYS, "pbftv_register_keys has not been called");
   return run_sharded(ctx, n, [&](Device& d, Shard s) -> int {
     const uint64_t m = s.hi - s.lo;
     Packer p;
@@ -2961,7 +3045,7 @@ int pbftv_flush_replies(pbftv_ctx* ctx, uint64_t n, const int64_t* view_ids, con
     const auto cid = p.add_str(client_ids, client_id_off, client_id_len, s.lo, s.hi);
     const auto nid = p.add_str(node_ids, node_id_off, node_id_len, s.lo, s.hi);
     const auto res = p.add_str(results, result_off, result_len, s.lo, s.hi);
-    const size_t o_sig = sig ? p.add(sig_rs + 64 * s.lo, 64 * m) : 0, o_key = sig ? p.add(key_idx + s.lo, 4 * m) : 0;
+    const size_t o_sig = sig ? p.add(sig_rs + 64 * s.lo, 64 * m) : 0, o_key = sig ? add_signer(p, by, s.lo, m) : 0;
     std::lock_guard<std::mutex> lk(d.mu);
     HIP_TRY(hipSetDevice(d.id));
     int rc = upload(d, p);
@@ -2974,14 +3058,36 @@ int pbftv_flush_replies(pbftv_ctx* ctx, uint64_t n, const int64_t* view_ids, con
     });
     if (rc != PBFTV_OK) return rc;
     if (sig) {
-      HIP_TRY(d.bitmap.ensure((m + 7) / 8 + 8));
-      rc = verify_on_device(d, d.digests.as<uint8_t>(), at<uint8_t>(d, o_sig), at<uint32_t>(d, o_key), m,
-                            d.bitmap.as<uint8_t>(), d.stream);
+      rc = flush_verify(d, by, o_sig, o_key, m);
       if (rc != PBFTV_OK) return rc;
     }
     return results_out(d, s.lo, m, {{kDigests, d.digests.p, out_digests},
                                     {kBitmap, d.bitmap.p, sig ? out_sig_bitmap : nullptr}});
   });
+}
+
+int pbftv_flush_replies(pbftv_ctx* ctx, uint64_t n, const int64_t* view_ids, const int64_t* timestamps,
+                        const uint8_t* client_ids, const uint64_t* client_id_off, const uint32_t* client_id_len,
+                        const uint8_t* node_ids, const uint64_t* node_id_off, const uint32_t* node_id_len,
+                        const uint8_t* results, const uint64_t* result_off, const uint32_t* result_len,
+                        const uint8_t* sig_rs, const uint32_t* key_idx, uint8_t* out_digests,
+                        uint8_t* out_sig_bitmap) {
+  return flush_replies_by(ctx, n, view_ids, timestamps, client_ids, client_id_off, client_id_len, node_ids,
+                          node_id_off, node_id_len, results, result_off, result_len, sig_rs,
+                          registered_signer(key_idx), out_digests, out_sig_bitmap);
+}
+
+int pbftv_flush_replies_wirekey(pbftv_ctx* ctx, uint64_t n, const int64_t* view_ids, const int64_t* timestamps,
+                                const uint8_t* client_ids, const uint64_t* client_id_off,
+                                const uint32_t* client_id_len, const uint8_t* node_ids, const uint64_t* node_id_off,
+                                const uint32_t* node_id_len, const uint8_t* results, const uint64_t* result_off,
+                                const uint32_t* result_len, const uint8_t* sig_rs, const uint8_t* keys,
+                                int key_format, uint8_t* out_digests, uint8_t* out_sig_bitmap) {
+  const uint64_t stride = pbftv_key_bytes(key_format);
+  if (!stride) return fail(PBFTV_EINVAL, "unknown key format");
+  return flush_replies_by(ctx, n, view_ids, timestamps, client_ids, client_id_off, client_id_len, node_ids,
+                          node_id_off, node_id_len, results, result_off, result_len, sig_rs,
+                          FlushSigner{nullptr, keys, key_format, stride}, out_digests, out_sig_bitmap);
 }
 
 int pbftv_digest_reply_batch(pbftv_ctx* ctx, uint64_t n, const int64_t* view_ids, const int64_t* timestamps,

@@ -24,6 +24,11 @@ PBFTV_EDEVICE = -3
 PBFTV_ENOMEM = -4
 PBFTV_ENOKEYS = -5
 
+# key formats of the *_wirekey entry points (include/pbftv.h PBFTV_KEY_*)
+KEY_XY = 0                 # X||Y, 64 B
+KEY_SEC1_COMPRESSED = 1    # 02|03 || X, 33 B
+KEY_SEC1_UNCOMPRESSED = 2  # 04 || X || Y, 65 B
+
 _u8p = ctypes.POINTER(ctypes.c_uint8)
 _u32p = ctypes.POINTER(ctypes.c_uint32)
 _u64p = ctypes.POINTER(ctypes.c_uint64)
@@ -138,6 +143,15 @@ def lib() -> ctypes.CDLL:
         "pbftv_ecdsa_p256_verify_pubkey_batch": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_uint64, _vp]),
         "pbftv_ecdsa_p256_verify_pubkey_batch_dev": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, _vp,
                                                                     ctypes.c_uint64, _vp, _vp]),
+        "pbftv_key_bytes": (ctypes.c_uint32, [ctypes.c_int]),
+        "pbftv_ecdsa_p256_verify_wirekey_batch": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_uint64,
+                                                                 _vp]),
+        "pbftv_ecdsa_p256_verify_wirekey_batch_dev": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, _vp, ctypes.c_int,
+                                                                     ctypes.c_uint64, _vp, _vp]),
+        "pbftv_flush_requests_wirekey": (ctypes.c_int, [_vp, ctypes.c_uint64] + [_vp] * 10 + [ctypes.c_int] +
+                                         [_vp] * 4),
+        "pbftv_flush_replies_wirekey": (ctypes.c_int, [_vp, ctypes.c_uint64] + [_vp] * 13 + [ctypes.c_int] +
+                                        [_vp] * 2),
         "pbftv_qc_verify": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_uint64, ctypes.c_uint32, _vp,
                                            ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_int)]),
     }
@@ -155,6 +169,11 @@ def header_symbols() -> list[str]:
         text = f.read()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     return sorted(set(re.findall(r"\b(pbftv_[a-z0-9_]+)\s*\(", text)))
+
+
+def key_bytes(key_format: int) -> int:
+    """pbftv_key_bytes: bytes per key of a format (64 / 33 / 65); 0 for an unknown one."""
+    return int(lib().pbftv_key_bytes(key_format))
 
 
 def _ptr(a) -> int | None:
@@ -408,6 +427,19 @@ def _sig_inputs(n: int, sigs, key_idx, what: str):
     if sigs.shape != (n, 64) or key_idx.shape != (n,):
         raise ValueError(f"{what}: sigs must be (n, 64) uint8 and key_idx (n,)")
     return sigs, key_idx, np.zeros((n + 7) // 8 + 1, np.uint8)
+
+
+def _wirekey_inputs(n: int, sigs, keys, key_format: int, what: str):
+    stride = key_bytes(key_format)
+    if not stride:
+        raise ValueError(f"{what}: unknown key format {key_format}")
+    if sigs is None:
+        return None, None, None
+    sigs = np.ascontiguousarray(sigs, np.uint8)
+    keys = np.ascontiguousarray(keys, np.uint8)
+    if sigs.shape != (n, 64) or keys.size != n * stride:
+        raise ValueError(f"{what}: sigs must be (n, 64) uint8 and keys n * {stride} bytes")
+    return sigs, keys, np.zeros((n + 7) // 8 + 1, np.uint8)
 
 
 def _states(n: int, states, state_idx, what: str, with_digests: bool):
@@ -754,6 +786,35 @@ class Verifier:
         _check(self._L.pbftv_flush_replies(self._h, n, *cols.args(), _ptr(S), _ptr(K), _ptr(out_d), _ptr(sbm)))
         return (out_d[:n] if out_d is not None else None, bitmap_to_bool(sbm, n) if sbm is not None else None)
 
+    def flush_requests_wirekey(self, cols: "RequestColumns", sigs=None, keys=None, key_format: int = KEY_XY,
+                               assigned_seqs=None, digests: bool = True):
+        """pbftv_flush_requests_wirekey: flush_requests with message i's key carried
+        in keys (packed at key_bytes(key_format)) instead of named by index; needs no
+        registered keys.  (digests | None, sig_ok | None, consensus digests | None)."""
+        n = cols.n
+        S, K, sbm = _wirekey_inputs(n, sigs, keys, key_format, "flush_requests_wirekey")
+        out_d = np.zeros((max(n, 1), 32), np.uint8) if digests else None
+        aseq = out_c = None
+        if assigned_seqs is not None:
+            aseq = np.ascontiguousarray(assigned_seqs, np.int64)
+            if aseq.shape != (n,):
+                raise ValueError("flush_requests_wirekey: assigned_seqs must be (n,)")
+            out_c = np.zeros((max(n, 1), 32), np.uint8)
+        _check(self._L.pbftv_flush_requests_wirekey(self._h, n, *cols.args(), _ptr(S), _ptr(K), key_format,
+                                                    _ptr(aseq), _ptr(out_d), _ptr(sbm), _ptr(out_c)))
+        return (out_d[:n] if out_d is not None else None, bitmap_to_bool(sbm, n) if sbm is not None else None,
+                out_c[:n] if out_c is not None else None)
+
+    def flush_replies_wirekey(self, cols: "ReplyColumns", sigs=None, keys=None, key_format: int = KEY_XY,
+                              digests: bool = True):
+        """pbftv_flush_replies_wirekey: (digests | None, sig_ok | None)."""
+        n = cols.n
+        S, K, sbm = _wirekey_inputs(n, sigs, keys, key_format, "flush_replies_wirekey")
+        out_d = np.zeros((max(n, 1), 32), np.uint8) if digests else None
+        _check(self._L.pbftv_flush_replies_wirekey(self._h, n, *cols.args(), _ptr(S), _ptr(K), key_format,
+                                                   _ptr(out_d), _ptr(sbm)))
+        return (out_d[:n] if out_d is not None else None, bitmap_to_bool(sbm, n) if sbm is not None else None)
+
     def flush_preprepares(self, cols: "PrePrepareColumns", sigs=None, key_idx=None, states=None, state_idx=None,
                           digests: bool = True, req_digests: bool = False):
         """pbftv_flush_preprepares: (digests | None, request digests | None, sig_ok | None, msg_ok | None).
@@ -837,6 +898,29 @@ class Verifier:
                                 stream: int | None = None):
         _check(self._L.pbftv_ecdsa_p256_verify_pubkey_batch_dev(self._h, dev, d_hashes, d_sigs, d_pub_xy, n,
                                                                 d_bitmap, stream))
+
+    def verify_wirekey_batch(self, hashes: np.ndarray, sig_rs: np.ndarray, keys: np.ndarray,
+                             key_format: int) -> np.ndarray:
+        """pbftv_ecdsa_p256_verify_wirekey_batch: signature i under the key at
+        keys[key_bytes(key_format) * i] (KEY_XY, KEY_SEC1_COMPRESSED or
+        KEY_SEC1_UNCOMPRESSED); a key that fails decoding gives a 0 bit."""
+        stride = key_bytes(key_format)
+        if not stride:
+            raise ValueError(f"verify_wirekey_batch: unknown key format {key_format}")
+        hashes = np.ascontiguousarray(hashes, np.uint8).reshape(-1, 32)
+        sig_rs = np.ascontiguousarray(sig_rs, np.uint8).reshape(-1, 64)
+        keys = np.ascontiguousarray(keys, np.uint8).reshape(-1, stride)
+        n = hashes.shape[0]
+        assert sig_rs.shape[0] == n and keys.shape[0] == n
+        bm = np.zeros((n + 7) // 8 + 1, np.uint8)
+        _check(self._L.pbftv_ecdsa_p256_verify_wirekey_batch(self._h, hashes.ctypes.data, sig_rs.ctypes.data,
+                                                             keys.ctypes.data, key_format, n, bm.ctypes.data))
+        return bitmap_to_bool(bm, n)
+
+    def verify_wirekey_batch_dev(self, dev: int, d_hashes: int, d_sigs: int, d_keys: int, key_format: int, n: int,
+                                 d_bitmap: int, stream: int | None = None):
+        _check(self._L.pbftv_ecdsa_p256_verify_wirekey_batch_dev(self._h, dev, d_hashes, d_sigs, d_keys, key_format,
+                                                                 n, d_bitmap, stream))
 
     def sha256_order_dev(self, dev: int, d_lengths: int, n: int, d_order: int, stream: int | None = None):
         _check(self._L.pbftv_sha256_order_dev(self._h, dev, d_lengths, n, d_order, stream))

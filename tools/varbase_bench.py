@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Throughput of the verify under unregistered keys
-(pbftv_ecdsa_p256_verify_pubkey_batch_dev) on one GPU, beside the CPU baseline
-on the same inputs.
+(pbftv_ecdsa_p256_verify_pubkey_batch_dev, or with --key-format compressed /
+uncompressed pbftv_ecdsa_p256_verify_wirekey_batch_dev on the same keys in SEC1
+wire form) on one GPU, beside the CPU baseline on the same inputs.
 
 The batch: n OpenSSL-signed signatures (tools/synth.py config 4: all distinct,
 1 % corrupted over the eight corruption classes) over a pool of `--keys`
@@ -32,9 +33,19 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 import synth  # noqa: E402
-from simple_pbft_amd import Verifier  # noqa: E402
+from simple_pbft_amd import KEY_SEC1_COMPRESSED, KEY_SEC1_UNCOMPRESSED, KEY_XY, Verifier  # noqa: E402
 
 K_SCALARS, K_VARBASE = 0, 5
+KEY_FORMATS = {"xy": KEY_XY, "compressed": KEY_SEC1_COMPRESSED, "uncompressed": KEY_SEC1_UNCOMPRESSED}
+
+
+def wire_keys(P, fmt):
+    """the X||Y keys P (n, 64) as a packed column in fmt (elliptic.Marshal / MarshalCompressed's bytes)"""
+    if fmt == KEY_XY:
+        return P
+    if fmt == KEY_SEC1_UNCOMPRESSED:
+        return np.ascontiguousarray(np.concatenate([np.full((len(P), 1), 4, np.uint8), P], axis=1))
+    return np.ascontiguousarray(np.concatenate([(2 + (P[:, 63:64] & 1)).astype(np.uint8), P[:, :32]], axis=1))
 
 
 def cpu_batch(so_name, fn_name, pub, H, S, K, sample, threads):
@@ -62,6 +73,8 @@ def main():
     ap.add_argument("--cpu-threads", type=int, default=16)
     ap.add_argument("--cpu-sample", type=int, default=262144)
     ap.add_argument("--oracle-sample", type=int, default=8192)
+    ap.add_argument("--key-format", choices=sorted(KEY_FORMATS), default="xy",
+                    help="how each signature's key is carried (xy: the pubkey entry point)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     assert a.steps >= 5 and a.keys >= 1
@@ -69,7 +82,10 @@ def main():
     pub, H, S, K, ok = synth.config4(a.n, n_keys=a.keys)
     P = np.ascontiguousarray(pub[K])
     n = a.n
-    res = {"metric": "ecdsa_p256_verify_pubkey_batch", "n": n, "keys": a.keys, "steps": a.steps,
+    fmt = KEY_FORMATS[a.key_format]
+    W = wire_keys(P, fmt)
+    res = {"metric": "ecdsa_p256_verify_pubkey_batch" if fmt == KEY_XY else "ecdsa_p256_verify_wirekey_batch",
+           "key_format": a.key_format, "key_bytes": int(W.shape[1]), "n": n, "keys": a.keys, "steps": a.steps,
            "warmup": a.warmup, "corrupted": int((~ok).sum())}
 
     hip = ctypes.CDLL("libamdhip64.so")  # the runtime libpbftv.so already loaded (same soname)
@@ -81,12 +97,15 @@ def main():
 
     with Verifier(device_mask=1) as v:
         st = vp(v.stream(0))
-        dh, ds, dp = v.to_device(0, H), v.to_device(0, S), v.to_device(0, P)
+        dh, ds, dp = v.to_device(0, H), v.to_device(0, S), v.to_device(0, W)
         db = v.alloc(0, (n + 7) // 8 + 8)
         db.zero()
 
         def step():
-            v.verify_pubkey_batch_dev(0, dh.ptr, ds.ptr, dp.ptr, n, db.ptr)
+            if fmt == KEY_XY:
+                v.verify_pubkey_batch_dev(0, dh.ptr, ds.ptr, dp.ptr, n, db.ptr)
+            else:
+                v.verify_wirekey_batch_dev(0, dh.ptr, ds.ptr, dp.ptr, fmt, n, db.ptr)
 
         step()  # first use: the G table, the scratch
         v.sync(0)
