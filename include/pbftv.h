@@ -234,8 +234,16 @@ int pbftv_digest_check_batch(pbftv_ctx* ctx, const uint8_t* data, const uint64_t
                              const uint8_t* expected, uint64_t n, uint8_t* out_bitmap);
 
 /* Device-resident form on device index dev (0..pbftv_device_count-1).  The
- * data buffer must be readable 4 bytes past the end of every message
- * (pbftv_dev_alloc / hipMalloc allocations are).  order (may be NULL) is a lane ->
+ * data buffer must be readable
+ *   - over every 128-byte-aligned line that holds a byte of a message, or the
+ *     position of an empty message that is not on a line boundary: the default
+ *     kernel (k_sha256_ring) fetches whole lines, so it reads up to 127 bytes
+ *     before a message's first byte and up to 127 after its last;
+ *   - over every 4-byte-aligned dword that does, so less than 4 bytes past the
+ *     end of a message: the PBFTV_SHA_RING=0 kernel (k_sha256) reads those.
+ * Memory mapped in pages (pbftv_dev_alloc / hipMalloc allocations, and ranges
+ * inside them) meets both, as a line never crosses a page; those bytes are
+ * read and masked off, never hashed.  order (may be NULL) is a lane ->
  * message permutation; pbftv_sha256_order_dev builds one that groups messages
  * by block count.  d_expected/d_bitmap may be NULL (digests only); d_bitmap
  * must be ceil(n/32)*4 bytes when used. */
@@ -302,6 +310,11 @@ int64_t pbftv_ecdsa_der_to_rs_batch(const uint8_t* data, const uint64_t* offsets
  * column-wise, the Go-JSON preimages are built on the GPU (one lane per
  * message, same encoder as pbftv_gojson_*) and hashed there.  client_ids /
  * operations are concatenated byte strings with per-item offsets/lengths.
+ * String columns, here and in every message-batch call below (digest_*_batch,
+ * flush_*): the strings may lie in any order in their blob, share bytes, and
+ * have other bytes before and between them (those are copied with the span
+ * the strings cover, and never encoded).  The offset of a string of length 0
+ * is not read: it may hold any value, inside the blob or not.
  * out_digests: n*32 raw bytes. */
 int pbftv_digest_request_batch(pbftv_ctx* ctx, uint64_t n, const int64_t* timestamps, const uint8_t* client_ids,
                                const uint64_t* client_id_off, const uint32_t* client_id_len, const uint8_t* operations,
