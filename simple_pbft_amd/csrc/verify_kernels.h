@@ -999,9 +999,11 @@ __device__ __forceinline__ void inv_mod_n_wave(fe& D, const uint32_t x[8]) {
   A = limbs_center(A, top);
   B = limbs_center(B, top);
   int32_t eta = -1;
-  // every input takes >= 17 batches since f starts at n: the first 14 skip the
-  // g == 0 test (a batch with g = 0 leaves f and d unchanged), so each batch
-  // ends in one branch
+  // no input found takes fewer than 16 batches since f starts at n (random
+  // ones take 17 to 19, seven powers of two take 16; the search and its
+  // histogram: tests/test_scalar_cases.py test_batch_counts): the first 14 skip
+  // the g == 0 test for speed only (a batch with g = 0 leaves f and d
+  // unchanged), so each of them ends in one branch
 #pragma unroll 1
   for (int it = 0; it < 14; ++it) inv_batch<false>(A, B, eta, nl, top, row);
 #pragma unroll 1
