@@ -7,8 +7,10 @@
 // varbase.h's verify against the oracle.  Built as a shared object for the
 // test, and with -DSEC1_MAIN as a stand-alone program (own main, for a
 // -fsanitize=address,undefined build) that decodes every multiple k G,
-// k = 1..64, in both formats and both parities, and a stream of random X.
-// Never linked into the product library.
+// k = 1..64, in both formats and both parities, and a stream of random X, and
+// -- given a dump of tests/carried_cases.py's combined set as its second
+// argument -- decodes and verifies that set's compressed keys against the
+// recorded values.  Never linked into the product library.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -17,6 +19,9 @@
 
 #include "../../simple_pbft_amd/csrc/sec1.h"
 #include "../../simple_pbft_amd/csrc/varbase.h"
+#if defined(SEC1_MAIN)
+#include "carried_dump.h"
+#endif
 
 using namespace pbftv;
 
@@ -238,6 +243,28 @@ int main(int argc, char** argv) {
   }
   if (n_random >= 64 && (with == 0 || without == 0)) ++bad;
   printf("sec1: %d mismatches (%d X with a point, %d without)\n", bad, with, without);
+  if (argc > 2) {  // the carried-key set under its compressed keys: the decode, then the verify
+    CarriedDump d;
+    if (!d.read(argv[2])) {
+      fprintf(stderr, "cannot read %s\n", argv[2]);
+      return 2;
+    }
+    std::vector<uint8_t> xy(64 * d.n), ok(d.n), out(d.n);
+    h_sec1_decode(d.n, d.comp.data(), kKeySec1Compressed, xy.data(), ok.data());
+    std::vector<uint32_t> gtab(h_sec1_g_table_words());
+    h_sec1_build_g_table(gtab.data());
+    h_sec1_verify_batch(d.n, d.hashes.data(), d.sigs.data(), d.comp.data(), kKeySec1Compressed, gtab.data(), out.data());
+    int wrong = 0, rejected = 0;
+    for (uint64_t i = 0; i < d.n; ++i) {
+      rejected += !ok[i];
+      if (ok[i] != d.comp_ok[i] || memcmp(&xy[64 * i], &d.comp_xy[64 * i], 64) || out[i] != d.want_comp[i]) {
+        ++wrong;
+        fprintf(stderr, "carried mismatch: row %llu (key %d, bit %d)\n", (unsigned long long)i, ok[i], out[i]);
+      }
+    }
+    printf("carried: %d mismatches of %llu (%d keys rejected)\n", wrong, (unsigned long long)d.n, rejected);
+    bad += wrong;
+  }
   return bad != 0;
 }
 #endif

@@ -7,7 +7,9 @@
 // object for the test, and with -DVARBASE_MAIN as a stand-alone program (own
 // main, for a -fsanitize=address,undefined build) that checks the ladder and
 // the exact rerun against the G comb alone on edge scalars and a random
-// stream.  Never linked into the product library.
+// stream, and -- given a dump of tests/carried_cases.py's combined set as its
+// second argument -- walks that set through h_vb_verify_batch against the
+// recorded bits.  Never linked into the product library.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -15,6 +17,9 @@
 #include <vector>
 
 #include "../../simple_pbft_amd/csrc/varbase.h"
+#if defined(VARBASE_MAIN)
+#include "carried_dump.h"
+#endif
 
 using namespace pbftv;
 
@@ -257,6 +262,26 @@ int main(int argc, char** argv) {
     bad += check(gtab.data(), u1, u2, 0, "random");
   }
   printf("varbase: %d mismatches\n", bad);
+  if (argc > 2) {  // the carried-key set: accept bits, and the rerun bit where it is pinned
+    CarriedDump d;
+    if (!d.read(argv[2])) {
+      fprintf(stderr, "cannot read %s\n", argv[2]);
+      return 2;
+    }
+    std::vector<uint8_t> out(d.n);
+    std::vector<int> paths(d.n);
+    h_vb_verify_batch(d.n, d.hashes.data(), d.sigs.data(), d.xy.data(), gtab.data(), out.data(), paths.data());
+    int wrong = 0, reruns = 0;
+    for (uint64_t i = 0; i < d.n; ++i) {
+      reruns += paths[i] & 1;
+      if (out[i] != d.want_xy[i] || (d.rerun[i] != 255 && (paths[i] & 1) != d.rerun[i])) {
+        ++wrong;
+        fprintf(stderr, "carried mismatch: row %llu (bit %d, rerun %d)\n", (unsigned long long)i, out[i], paths[i] & 1);
+      }
+    }
+    printf("carried: %d mismatches of %llu (%d reruns)\n", wrong, (unsigned long long)d.n, reruns);
+    bad += wrong;
+  }
   return bad != 0;
 }
 #endif
