@@ -366,6 +366,58 @@ func (x *Ctx) VerifyWireKeyBatch(hashes [][32]byte, sigs [][64]byte, keys []byte
 	return bits(bm, n), nil
 }
 
+// derColumn packs signatures as ecdsa.SignASN1 wrote them into the string
+// column the *_der calls take.
+func derColumn(sigs [][]byte) column { return packBytes(sigs) }
+
+// VerifySigsASN1 is VerifySigs with the signatures as they travel: sigs[i] is
+// the ASN.1 DER that ecdsa.SignASN1 wrote and ecdsa.VerifyASN1 reads, parsed
+// on the GPU with go1.19's strictness in the same round trip as the verify
+// (pbftv_ecdsa_p256_verify_der_batch).  An encoding VerifyASN1 would refuse
+// gives false, not an error.
+func (x *Ctx) VerifySigsASN1(hashes [][32]byte, sigs [][]byte, keyIdx []uint32) ([]bool, error) {
+	n := len(hashes)
+	if len(sigs) != n || len(keyIdx) != n {
+		return nil, &Error{Code: EINVAL, Msg: "hashes, sigs and keyIdx differ in length"}
+	}
+	if n == 0 {
+		return nil, nil
+	}
+	d := derColumn(sigs)
+	bm := make([]byte, (n+7)/8)
+	err := call(func() C.int { return C.pbftv_ecdsa_p256_verify_der_batch(x.c, (*C.uint8_t)(unsafe.Pointer(&hashes[0])),
+		u8(d.blob), u64(d.off), u32(d.ln), u32(keyIdx), C.uint64_t(n), u8(bm)) })
+	if err != nil {
+		return nil, err
+	}
+	return bits(bm, n), nil
+}
+
+// VerifyWireKeyBatchASN1 is VerifyWireKeyBatch with DER signatures: key and
+// signature both as they came off the wire
+// (pbftv_ecdsa_p256_verify_wirekey_der_batch).
+func (x *Ctx) VerifyWireKeyBatchASN1(hashes [][32]byte, sigs [][]byte, keys []byte, format KeyFormat) ([]bool, error) {
+	n := len(hashes)
+	if len(sigs) != n {
+		return nil, &Error{Code: EINVAL, Msg: "hashes and sigs differ in length"}
+	}
+	kp, err := wireKeys(keys, format, n)
+	if err != nil {
+		return nil, err
+	}
+	if n == 0 {
+		return nil, nil
+	}
+	d := derColumn(sigs)
+	bm := make([]byte, (n+7)/8)
+	err = call(func() C.int { return C.pbftv_ecdsa_p256_verify_wirekey_der_batch(x.c, (*C.uint8_t)(unsafe.Pointer(&hashes[0])),
+		u8(d.blob), u64(d.off), u32(d.ln), kp, C.int(format), C.uint64_t(n), u8(bm)) })
+	if err != nil {
+		return nil, err
+	}
+	return bits(bm, n), nil
+}
+
 // QCVerify verifies one quorum certificate and counts it: reached =
 // accepted >= quorum (quorum = 2f reproduces prepared()/committed(),
 // pbft/consensus/pbft_impl.go:207-232; 2f+1 checks a PBFT certificate).

@@ -177,15 +177,22 @@ int pbftv_set_latency_path_max(pbftv_ctx* ctx, uint64_t n);
  * 2 = sha256, 3 = ecdsa wave-per-signature (small batches), 4 = Go-JSON message
  * encoder (digest / flush batches), 5 = ecdsa under unregistered keys (the
  * ladder kernel of pbftv_ecdsa_p256_verify_pubkey_batch).  pbftv_kernel_time_ms synchronises the device's stream and
- * returns the summed milliseconds and the launch count since the last reset. */
+ * returns the summed milliseconds and the launch count since the last reset.
+ * Timing id 6, PBFTV_K_ECDSA_DER, is the launch of k_der_to_rs (DER signatures
+ * normalised to r||s: pbftv_ecdsa_der_to_rs_batch_dev and every *_der verify
+ * and flush), timed and reset with the others.  pbftv_kernel_time_ms accepts
+ * the ids 0..5 it always did (any other is PBFTV_EINVAL, as callers may rely
+ * on); id 6 is read through pbftv_der_kernel_time_ms, same outputs. */
 #define PBFTV_K_ECDSA_SCALARS 0
 #define PBFTV_K_ECDSA_COMB 1
 #define PBFTV_K_SHA256 2
 #define PBFTV_K_ECDSA_WAVE 3
 #define PBFTV_K_GOJSON 4
 #define PBFTV_K_ECDSA_VARBASE 5
+#define PBFTV_K_ECDSA_DER 6
 int pbftv_set_kernel_timing(pbftv_ctx* ctx, int enable);
 int pbftv_kernel_time_ms(pbftv_ctx* ctx, int dev, int kernel, double* out_ms, uint64_t* out_launches);
+int pbftv_der_kernel_time_ms(pbftv_ctx* ctx, int dev, double* out_ms, uint64_t* out_launches);
 int pbftv_reset_kernel_times(pbftv_ctx* ctx);
 /* Diagnostics of the last latency-path call (n <= 2048) on device dev:
  * out[0] = host ns from entry to the request being handed over (bell rung or
@@ -300,7 +307,11 @@ uint64_t pbftv_gojson_preprepare(int64_t view_id, int64_t sequence_id, const cha
  * big-endian, the sig_rs layout of pbftv_ecdsa_p256_verify_batch).  Returns 1
  * when parsed with 0 <= r, s < 2^256, 0 when Go would reject it at the parse
  * or range check (out_rs zeroed, so the verify yields a 0 bit), PBFTV_EINVAL
- * on null pointers.  The batch form returns the number parsed (or < 0). */
+ * on null pointers.  The batch form returns the number parsed (or < 0).
+ * These two run on the host, one signature after another (25-40 ns each);
+ * a caller that verifies what it parses hands the encodings to the *_der
+ * calls below (after the *_wirekey ones) instead, which run the same parser
+ * on the device in the round trip of the verify. */
 int pbftv_ecdsa_der_to_rs(const uint8_t* der, uint64_t der_len, uint8_t* out_rs);
 int64_t pbftv_ecdsa_der_to_rs_batch(const uint8_t* data, const uint64_t* offsets, const uint32_t* lengths,
                                     uint64_t n, uint8_t* out_rs);
@@ -550,6 +561,124 @@ int pbftv_flush_replies_wirekey(pbftv_ctx* ctx, uint64_t n, const int64_t* view_
                                 const uint32_t* node_id_len, const uint8_t* results, const uint64_t* result_off,
                                 const uint32_t* result_len, const uint8_t* sig_rs, const uint8_t* keys,
                                 int key_format, uint8_t* out_digests, uint8_t* out_sig_bitmap);
+
+/* ---- signatures as ASN.1 DER, parsed on the device ----------------------
+ * Go holds a signature as the []byte that ecdsa.SignASN1 wrote and
+ * ecdsa.VerifyASN1 reads.  Every call below takes that form as a signature
+ * column (der, der_off, der_len) -- signature i is the der_len[i] bytes at
+ * der + der_off[i] -- where the call of the same name without _der takes
+ * sig_rs, and runs the parser of pbftv_ecdsa_der_to_rs on the device (one lane
+ * per signature, k_der_to_rs) in the same round trip as the hash and the
+ * verify.  The column follows the string-column rules above: any order,
+ * shared bytes, other bytes before and between the encodings, and the offset
+ * of an encoding of length 0 is not read.  A signature that does not parse
+ * (or whose r or s is outside [0, 2^256)) is a 0 bit, never an error.  n = 0
+ * returns PBFTV_OK and writes nothing; n >= 2^32 is PBFTV_EINVAL.  Every
+ * other semantic, argument check and the PBFTV_ENOKEYS behaviour is that of
+ * the r||s call of the same name.  (pbftv_qc_verify has no DER form: a
+ * certificate has 3 to 67 signatures, and the host parse is noise there.)
+ *
+ * No encoding longer than 72 bytes parses, so only the first min(der_len[i],
+ * 72) bytes of an encoding are ever read, whatever der_len[i] claims.
+ *
+ * pbftv_ecdsa_der_to_rs_batch_dev is the building block: d_out_rs (64 n B,
+ * 16-B aligned) receives r||s or zeros, d_parsed_bitmap (may be NULL) the
+ * LSB-first bitmap of the signatures that parsed (ceil(n/8) B, padding bits
+ * zero).  Enqueued on `stream` (NULL: the context's stream), not synchronised;
+ * it composes with any *_dev verify on the same stream, and its in-flight work
+ * is counted by the context's wait before key changes and by pbftv_dev_free
+ * like any other *_dev call.
+ * Readability (every *_dev form here): the data buffer must be readable over
+ * every 4-byte-aligned dword that holds one of the first min(der_len[i], 72)
+ * bytes of an encoding, so less than 4 bytes before its first byte and past
+ * that prefix -- the dword rule of pbftv_sha256_batch_dev.  Memory mapped in
+ * pages (pbftv_dev_alloc / hipMalloc allocations, and ranges inside them)
+ * meets it.  The host forms pad their own device copy.
+ *
+ * pbftv_ecdsa_p256_verify_der_batch: registered keys.  Batches up to the
+ * latency-path maximum are parsed on the host (the same parser) and handed to
+ * pbftv_ecdsa_p256_verify_batch, so an armed latency kernel keeps serving
+ * certificates exactly as for an r||s caller.  Larger ones are split into one
+ * shard per device; each shard copies its hashes, the span its encodings
+ * cover, their offsets and lengths and its key indices in, normalises and
+ * verifies on the device and copies its bitmap back -- simple copies, no
+ * chunk pipelining (unlike pbftv_ecdsa_p256_verify_batch).  The _dev form
+ * (hashes 16-B aligned) keeps the r||s column in one scratch per device that
+ * the library orders across streams: *_der batches enqueued on two streams of
+ * one device run one after the other, also on streams from
+ * pbftv_stream_create (the r||s forms overlap there; to overlap DER batches,
+ * normalise into buffers of your own with pbftv_ecdsa_der_to_rs_batch_dev and
+ * call the r||s verify).
+ * pbftv_ecdsa_p256_verify_wirekey_der_batch: carried keys (keys, key_format:
+ * as pbftv_ecdsa_p256_verify_wirekey_batch); no registered keys needed, read
+ * or disturbed. */
+int pbftv_ecdsa_der_to_rs_batch_dev(pbftv_ctx* ctx, int dev, const uint8_t* d_data, const uint64_t* d_offsets,
+                                    const uint32_t* d_lengths, uint64_t n, uint8_t* d_out_rs,
+                                    uint8_t* d_parsed_bitmap /* may be NULL */, void* stream);
+int pbftv_ecdsa_p256_verify_der_batch(pbftv_ctx* ctx, const uint8_t* hashes, const uint8_t* der,
+                                      const uint64_t* der_off, const uint32_t* der_len, const uint32_t* key_idx,
+                                      uint64_t n, uint8_t* out_bitmap);
+int pbftv_ecdsa_p256_verify_der_batch_dev(pbftv_ctx* ctx, int dev, const uint8_t* d_hashes, const uint8_t* d_der,
+                                          const uint64_t* d_der_off, const uint32_t* d_der_len,
+                                          const uint32_t* d_key_idx, uint64_t n, uint8_t* d_bitmap, void* stream);
+int pbftv_ecdsa_p256_verify_wirekey_der_batch(pbftv_ctx* ctx, const uint8_t* hashes, const uint8_t* der,
+                                              const uint64_t* der_off, const uint32_t* der_len, const uint8_t* keys,
+                                              int key_format, uint64_t n, uint8_t* out_bitmap);
+int pbftv_ecdsa_p256_verify_wirekey_der_batch_dev(pbftv_ctx* ctx, int dev, const uint8_t* d_hashes,
+                                                  const uint8_t* d_der, const uint64_t* d_der_off,
+                                                  const uint32_t* d_der_len, const uint8_t* d_keys, int key_format,
+                                                  uint64_t n, uint8_t* d_bitmap, void* stream);
+
+/* The six flushes with the signature column as DER: the encodings travel in
+ * the flush's one host->device copy, are normalised on the device after the
+ * hash, and the unchanged signature stage runs on the result -- still one GPU
+ * round trip per device.  A signature bitmap needs the DER column (der_off and
+ * der_len; der may be NULL only if every length is 0) and key_idx / keys. */
+int pbftv_flush_votes_der(pbftv_ctx* ctx, uint64_t n, const int64_t* view_ids, const int64_t* sequence_ids,
+                          const uint8_t* digests, const uint64_t* digest_off, const uint32_t* digest_len,
+                          const uint8_t* node_ids, const uint64_t* node_id_off, const uint32_t* node_id_len,
+                          const int64_t* msg_types, const uint8_t* der, const uint64_t* der_off,
+                          const uint32_t* der_len, const uint32_t* key_idx, uint32_t n_states,
+                          const int64_t* state_view_ids, const int64_t* state_last_seqs,
+                          const uint8_t* state_req_digests, const uint32_t* state_idx, uint8_t* out_digests,
+                          uint8_t* out_sig_bitmap, uint8_t* out_msg_bitmap);
+int pbftv_flush_preprepares_der(pbftv_ctx* ctx, uint64_t n, const int64_t* view_ids, const int64_t* sequence_ids,
+                                const uint8_t* digests, const uint64_t* digest_off, const uint32_t* digest_len,
+                                const uint8_t* has_request, const int64_t* req_timestamps,
+                                const uint8_t* req_client_ids, const uint64_t* req_client_id_off,
+                                const uint32_t* req_client_id_len, const uint8_t* req_operations,
+                                const uint64_t* req_operation_off, const uint32_t* req_operation_len,
+                                const int64_t* req_sequence_ids, const uint8_t* der, const uint64_t* der_off,
+                                const uint32_t* der_len, const uint32_t* key_idx, uint32_t n_states,
+                                const int64_t* state_view_ids, const int64_t* state_last_seqs,
+                                const uint32_t* state_idx, uint8_t* out_digests, uint8_t* out_req_digests,
+                                uint8_t* out_sig_bitmap, uint8_t* out_msg_bitmap);
+int pbftv_flush_requests_der(pbftv_ctx* ctx, uint64_t n, const int64_t* timestamps, const uint8_t* client_ids,
+                             const uint64_t* client_id_off, const uint32_t* client_id_len, const uint8_t* operations,
+                             const uint64_t* operation_off, const uint32_t* operation_len,
+                             const int64_t* sequence_ids, const uint8_t* der, const uint64_t* der_off,
+                             const uint32_t* der_len, const uint32_t* key_idx, const int64_t* assigned_seqs,
+                             uint8_t* out_digests, uint8_t* out_sig_bitmap, uint8_t* out_consensus_digests);
+int pbftv_flush_replies_der(pbftv_ctx* ctx, uint64_t n, const int64_t* view_ids, const int64_t* timestamps,
+                            const uint8_t* client_ids, const uint64_t* client_id_off, const uint32_t* client_id_len,
+                            const uint8_t* node_ids, const uint64_t* node_id_off, const uint32_t* node_id_len,
+                            const uint8_t* results, const uint64_t* result_off, const uint32_t* result_len,
+                            const uint8_t* der, const uint64_t* der_off, const uint32_t* der_len,
+                            const uint32_t* key_idx, uint8_t* out_digests, uint8_t* out_sig_bitmap);
+int pbftv_flush_requests_wirekey_der(pbftv_ctx* ctx, uint64_t n, const int64_t* timestamps, const uint8_t* client_ids,
+                                     const uint64_t* client_id_off, const uint32_t* client_id_len,
+                                     const uint8_t* operations, const uint64_t* operation_off,
+                                     const uint32_t* operation_len, const int64_t* sequence_ids, const uint8_t* der,
+                                     const uint64_t* der_off, const uint32_t* der_len, const uint8_t* keys,
+                                     int key_format, const int64_t* assigned_seqs, uint8_t* out_digests,
+                                     uint8_t* out_sig_bitmap, uint8_t* out_consensus_digests);
+int pbftv_flush_replies_wirekey_der(pbftv_ctx* ctx, uint64_t n, const int64_t* view_ids, const int64_t* timestamps,
+                                    const uint8_t* client_ids, const uint64_t* client_id_off,
+                                    const uint32_t* client_id_len, const uint8_t* node_ids,
+                                    const uint64_t* node_id_off, const uint32_t* node_id_len, const uint8_t* results,
+                                    const uint64_t* result_off, const uint32_t* result_len, const uint8_t* der,
+                                    const uint64_t* der_off, const uint32_t* der_len, const uint8_t* keys,
+                                    int key_format, uint8_t* out_digests, uint8_t* out_sig_bitmap);
 
 /* Quorum certificate: verify n signatures and count acceptances.
  * *out_accepted = popcount; *out_quorum = (*out_accepted >= quorum).  With

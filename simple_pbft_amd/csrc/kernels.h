@@ -211,6 +211,18 @@ hipError_t launch_varbase_keys(const uint8_t* keys, int key_format, uint64_t n, 
 hipError_t launch_varbase(const void* rec, const void* aux, uint64_t n, const uint32_t* gtab, void* tab,
                           uint64_t lanes, uint8_t* bitmap, hipStream_t st);
 
+// ---- DER signatures -> r||s (der_kernels.hip, der.h) ----
+// Signature i is the lengths[i] bytes at data + offsets[i] (a string column:
+// any order, overlaps and other bytes between the encodings allowed; the
+// offset of an encoding of length 0 is not read).  out_rs: 64 B per signature,
+// 16-B aligned, r||s big-endian or zeros where Go's VerifyASN1 parse or the
+// range 0 <= r, s < 2^256 rejects the encoding; parsed (may be null): the
+// LSB-first bitmap of those that parsed, ceil(n/8) B, padding bits zero.
+// Reads only 4-byte-aligned dwords that hold one of the first
+// min(lengths[i], 72) bytes of an encoding.  n < 2^32.
+hipError_t launch_der_to_rs(const uint8_t* data, const uint64_t* offsets, const uint32_t* lengths, uint64_t n,
+                            uint8_t* out_rs, uint8_t* parsed, hipStream_t st);
+
 // ---- SHA-256 (sha256_kernels.hip) ----
 // data must stay readable 4 bytes past every message end (device allocations are padded).
 // order: optional permutation (lane -> message), used for block-count bucketing.

@@ -31,6 +31,7 @@
 #include "gojson.h"
 #include "gojson_enc.h"
 #include "host/pending_frees.h"
+#include "der.h"
 #include "kernels.h"
 
 namespace {
@@ -346,6 +347,18 @@ struct Device {
   std::vector<std::pair<hipEvent_t, hipEvent_t>> pending[kKernels];
   double acc_ms[kKernels] = {0, 0, 0, 0, 0, 0};
   uint64_t launches[kKernels] = {0, 0, 0, 0, 0, 0};
+  // DER signatures (der_kernels.hip): the r||s column the normaliser writes for
+  // the *_der verifies and flushes (64 B per signature; one per device, every
+  // use ordered by the scratch event, also on streams that own a
+  // VerifyScratch) and timing id PBFTV_K_ECDSA_DER.  Kept apart from
+  // VerifyScratch and the arrays above, after every other member: no call
+  // that existed before the DER forms reads or writes any of it.
+  struct Der {
+    DevBuf rs;
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
+    double acc_ms = 0;
+    uint64_t launches = 0;
+  } der;
 };
 
 // key-order scratch: a fresh allocation gets its header zeroed (the sort's
@@ -1093,12 +1106,16 @@ struct Packer {
   struct Str {
     size_t data, off, len;
   };
-  Str add_str(const uint8_t* data, const uint64_t* off, const uint32_t* len, uint64_t lo, uint64_t hi) {
+  // clip: only the first `clip` bytes of each string count toward the span
+  // (a DER column: the normaliser reads no more of an encoding, der.h; the
+  // lengths go to the device as they are)
+  Str add_str(const uint8_t* data, const uint64_t* off, const uint32_t* len, uint64_t lo, uint64_t hi,
+              uint32_t clip = UINT32_MAX) {
     uint64_t a = UINT64_MAX, b = 0;
     for (uint64_t i = lo; i < hi; ++i)
       if (len[i]) {
         a = std::min(a, off[i]);
-        b = std::max(b, off[i] + len[i]);
+        b = std::max(b, off[i] + std::min(len[i], clip));
       }
     if (a > b) a = b = 0;
     if (b > a && data == nullptr) {
@@ -1661,6 +1678,21 @@ int pbftv_kernel_time_ms(pbftv_ctx* ctx, int dev, int kernel, double* out_ms, ui
   return PBFTV_OK;
 }
 
+// timing id PBFTV_K_ECDSA_DER (k_der_to_rs): a slot of its own (Device::der),
+// read here; pbftv_kernel_time_ms and its arrays stay as they were
+static hipError_t der_collect_times(Device& d);
+
+int pbftv_der_kernel_time_ms(pbftv_ctx* ctx, int dev, double* out_ms, uint64_t* out_launches) {
+  Device* d = dev_of(ctx, dev);
+  if (!d) return fail(PBFTV_EINVAL, "bad argument");
+  std::lock_guard<std::mutex> lk(d->mu);
+  HIP_TRY(hipSetDevice(d->id));
+  HIP_TRY(der_collect_times(*d));
+  if (out_ms) *out_ms = d->der.acc_ms;
+  if (out_launches) *out_launches = d->der.launches;
+  return PBFTV_OK;
+}
+
 int pbftv_reset_kernel_times(pbftv_ctx* ctx) {
   if (!ctx) return fail(PBFTV_EINVAL, "ctx is null");
   for (auto& dp : ctx->devs) {
@@ -1671,6 +1703,9 @@ int pbftv_reset_kernel_times(pbftv_ctx* ctx) {
       dp->acc_ms[k] = 0;
       dp->launches[k] = 0;
     }
+    HIP_TRY(der_collect_times(*dp));
+    dp->der.acc_ms = 0;
+    dp->der.launches = 0;
   }
   return PBFTV_OK;
 }
@@ -2647,6 +2682,216 @@ int pbftv_ecdsa_p256_verify_batch(pbftv_ctx* ctx, const uint8_t* hashes, const u
   });
 }
 
+// ---- signatures as ASN.1 DER, normalised on the device (der.h, der_kernels.hip) ----
+// The normaliser on stream st (d.mu held): reads and writes the caller's
+// buffers only.  Fenced for key changes and deferred frees like a verify that
+// uses no device scratch.
+static int der_on_device(Device& d, const uint8_t* d_data, const uint64_t* d_off, const uint32_t* d_len, uint64_t n,
+                         uint8_t* d_out_rs, uint8_t* d_parsed, hipStream_t st) {
+  if (!d.timing || !*d.timing) {
+    HIP_TRY(pbftv::launch_der_to_rs(d_data, d_off, d_len, n, d_out_rs, d_parsed, st));
+    return PBFTV_OK;
+  }
+  hipEvent_t a, b;  // (as timed(): events around the launch, collected by pbftv_der_kernel_time_ms)
+  HIP_TRY(hipEventCreate(&a));
+  HIP_TRY(hipEventCreate(&b));
+  (void)hipEventRecord(a, st);
+  const hipError_t e = pbftv::launch_der_to_rs(d_data, d_off, d_len, n, d_out_rs, d_parsed, st);
+  (void)hipEventRecord(b, st);
+  d.der.pending.push_back({a, b});
+  HIP_TRY(e);
+  return PBFTV_OK;
+}
+
+// the DER slot's pending events into its sums (collect_times for id 6)
+static hipError_t der_collect_times(Device& d) {
+  for (auto& pr : d.der.pending) {
+    HIP_TRY_E(hipEventSynchronize(pr.second));
+    float ms = 0;
+    HIP_TRY_E(hipEventElapsedTime(&ms, pr.first, pr.second));
+    d.der.acc_ms += ms;
+    d.der.launches += 1;
+    (void)hipEventDestroy(pr.first);
+    (void)hipEventDestroy(pr.second);
+  }
+  d.der.pending.clear();
+  return hipSuccess;
+}
+
+int pbftv_ecdsa_der_to_rs_batch_dev(pbftv_ctx* ctx, int dev, const uint8_t* d_data, const uint64_t* d_offsets,
+                                    const uint32_t* d_lengths, uint64_t n, uint8_t* d_out_rs,
+                                    uint8_t* d_parsed_bitmap, void* stream) {
+  if (!ctx || dev < 0 || dev >= (int)ctx->devs.size()) return fail(PBFTV_EINVAL, "bad context or device index");
+  if (n >> 32) return fail(PBFTV_EINVAL, "n must be below 2^32");
+  if (n == 0) return PBFTV_OK;
+  // (d_data may be null when every length is zero: the lengths live on the device)
+  if (!d_offsets || !d_lengths || !d_out_rs) return fail(PBFTV_EINVAL, "null buffer");
+  if ((uintptr_t)d_out_rs & 15u) return fail(PBFTV_EINVAL, "out_rs must be 16-B aligned");
+  if (((uintptr_t)d_offsets & 7u) || ((uintptr_t)d_lengths & 3u))
+    return fail(PBFTV_EINVAL, "offsets / lengths must be 8-B / 4-B aligned");
+  Device& d = *ctx->devs[dev];
+  std::lock_guard<std::mutex> lk(d.mu);
+  HIP_TRY(hipSetDevice(d.id));
+  hipStream_t st = pick_stream(d, stream);
+  note_busy(d, n, 0.05);
+  const int rc = der_on_device(d, d_data, d_offsets, d_lengths, n, d_out_rs, d_parsed_bitmap, st);
+  if (rc != PBFTV_OK) return rc;
+  HIP_TRY(fence_reader(d, st));
+  return PBFTV_OK;
+}
+
+// One batch with its signatures as a DER column on stream st (d.mu held): the
+// normaliser writes an ordinary r||s column into the device's DER scratch
+// (Device::der.rs, one per device: every use, on whatever stream, is ordered
+// by the scratch event, so DER batches on two streams follow one another),
+// then the unchanged verify runs on it -- under registered keys (d_key_idx)
+// or carried ones (d_keys in key_format).
+static int verify_der_on_device(Device& d, const uint8_t* d_hashes, const uint8_t* d_der, const uint64_t* d_off,
+                                const uint32_t* d_len, const uint32_t* d_key_idx, const uint8_t* d_keys,
+                                int key_format, uint64_t n, uint8_t* d_bitmap, hipStream_t st) {
+  if (n == 0) return PBFTV_OK;
+  if (!d_keys && !d.have_keys) return fail(PBFTV_ENOKEYS, "pbftv_register_keys has not been called");
+  HIP_TRY(d.der.rs.ensure(64 * n));
+  uint8_t* rs = d.der.rs.as<uint8_t>();
+  HIP_TRY(scratch_acquire(d, st));
+  int rc = der_on_device(d, d_der, d_off, d_len, n, rs, nullptr, st);
+  HIP_TRY(scratch_release(d, st));
+  if (rc != PBFTV_OK) return rc;
+  rc = d_keys ? varbase_on_device(d, d_hashes, rs, d_keys, key_format, n, d_bitmap, st)
+              : verify_on_device(d, d_hashes, rs, d_key_idx, n, d_bitmap, st);
+  // the verify read rs, whichever path it took and whichever scratch it used
+  // itself: the next user of rs on another stream waits for this point
+  if (rc == PBFTV_OK) HIP_TRY(scratch_release(d, st));
+  return rc;
+}
+
+int pbftv_ecdsa_p256_verify_der_batch_dev(pbftv_ctx* ctx, int dev, const uint8_t* d_hashes, const uint8_t* d_der,
+                                          const uint64_t* d_der_off, const uint32_t* d_der_len,
+                                          const uint32_t* d_key_idx, uint64_t n, uint8_t* d_bitmap, void* stream) {
+  if (!ctx || dev < 0 || dev >= (int)ctx->devs.size()) return fail(PBFTV_EINVAL, "bad context or device index");
+  if (n >> 32) return fail(PBFTV_EINVAL, "n must be below 2^32");
+  if (n == 0) return PBFTV_OK;
+  if (!d_hashes || !d_der_off || !d_der_len || !d_key_idx || !d_bitmap) return fail(PBFTV_EINVAL, "null buffer");
+  if ((uintptr_t)d_hashes & 15u) return fail(PBFTV_EINVAL, "hashes must be 16-B aligned");
+  Device& d = *ctx->devs[dev];
+  std::lock_guard<std::mutex> lk(d.mu);
+  HIP_TRY(hipSetDevice(d.id));
+  return verify_der_on_device(d, d_hashes, d_der, d_der_off, d_der_len, d_key_idx, nullptr, 0, n, d_bitmap,
+                              pick_stream(d, stream));
+}
+
+int pbftv_ecdsa_p256_verify_wirekey_der_batch_dev(pbftv_ctx* ctx, int dev, const uint8_t* d_hashes,
+                                                  const uint8_t* d_der, const uint64_t* d_der_off,
+                                                  const uint32_t* d_der_len, const uint8_t* d_keys, int key_format,
+                                                  uint64_t n, uint8_t* d_bitmap, void* stream) {
+  if (!ctx || dev < 0 || dev >= (int)ctx->devs.size()) return fail(PBFTV_EINVAL, "bad context or device index");
+  if (!pbftv_key_bytes(key_format)) return fail(PBFTV_EINVAL, "unknown key format");
+  if (n >> 32) return fail(PBFTV_EINVAL, "n must be below 2^32");
+  if (n == 0) return PBFTV_OK;
+  if (!d_hashes || !d_der_off || !d_der_len || !d_keys || !d_bitmap) return fail(PBFTV_EINVAL, "null buffer");
+  if (((uintptr_t)d_hashes | (uintptr_t)d_keys) & 15u) return fail(PBFTV_EINVAL, "hashes/keys must be 16-B aligned");
+  Device& d = *ctx->devs[dev];
+  std::lock_guard<std::mutex> lk(d.mu);
+  HIP_TRY(hipSetDevice(d.id));
+  return verify_der_on_device(d, d_hashes, d_der, d_der_off, d_der_len, nullptr, d_keys, key_format, n, d_bitmap,
+                              pick_stream(d, stream));
+}
+
+// A shard's DER column on the device (d.mu held, on d.stream): the span its
+// encodings cover -- of each only the first 72 bytes, all the normaliser reads
+// (der.h) -- copied into a padded buffer, the offsets rebased onto it.  `keep`
+// holds the rebased offsets until the caller has synchronised.
+static int der_column_in(Device& d, const uint8_t* der, const uint64_t* off, const uint32_t* len, uint64_t lo,
+                         uint64_t m, std::vector<uint64_t>& keep) {
+  uint64_t a = UINT64_MAX, b = 0;
+  for (uint64_t i = lo; i < lo + m; ++i)
+    if (len[i]) {
+      a = std::min(a, off[i]);
+      b = std::max(b, off[i] + std::min<uint32_t>(len[i], pbftv::kDerMaxBytes));
+    }
+  if (a > b) a = b = 0;
+  if (b > a && der == nullptr) return fail(PBFTV_EINVAL, "DER column: nonzero lengths with a null data pointer");
+  keep.resize(m);
+  for (uint64_t i = 0; i < m; ++i) keep[i] = len[lo + i] ? off[lo + i] - a : 0;
+  HIP_TRY(d.data.ensure(b - a + 64));
+  HIP_TRY(d.offsets.ensure(8 * m + 8));
+  HIP_TRY(d.lengths.ensure(4 * m + 4));
+  if (b > a) HIP_TRY(hipMemcpyAsync(d.data.p, der + a, b - a, hipMemcpyHostToDevice, d.stream));
+  HIP_TRY(hipMemcpyAsync(d.offsets.p, keep.data(), 8 * m, hipMemcpyHostToDevice, d.stream));
+  HIP_TRY(hipMemcpyAsync(d.lengths.p, len + lo, 4 * m, hipMemcpyHostToDevice, d.stream));
+  return PBFTV_OK;
+}
+
+// Host forms above the latency path: contiguous shards over the context's
+// devices; each copies its hashes, its DER span, offsets, lengths and signer
+// column in, normalises and verifies on its stream, and copies its bitmap
+// back (simple copies, no chunk pipelining).
+static int verify_der_host_sharded(pbftv_ctx* ctx, const uint8_t* hashes, const uint8_t* der, const uint64_t* der_off,
+                                   const uint32_t* der_len, const uint32_t* key_idx, const uint8_t* keys,
+                                   int key_format, uint64_t n, uint8_t* out_bitmap) {
+  const uint64_t stride = keys ? pbftv_key_bytes(key_format) : 0;
+  return run_sharded(ctx, n, [&](Device& d, Shard s) -> int {
+    std::lock_guard<std::mutex> lk(d.mu);
+    HIP_TRY(hipSetDevice(d.id));
+    const uint64_t m = s.hi - s.lo;
+    std::vector<uint64_t> keep;  // (source of an asynchronous copy: alive until d.stream has been synchronised)
+    const int rc = [&]() -> int {
+    int rc = der_column_in(d, der, der_off, der_len, s.lo, m, keep);
+    if (rc != PBFTV_OK) return rc;
+    HIP_TRY(d.hashes.ensure(32 * m + 64));
+    HIP_TRY(d.bitmap.ensure((m + 7) / 8 + 8));
+    HIP_TRY(hipMemcpyAsync(d.hashes.p, hashes + 32 * s.lo, 32 * m, hipMemcpyHostToDevice, d.stream));
+    if (keys) {
+      HIP_TRY(d.vb_pub.ensure(stride * m + 64));
+      HIP_TRY(hipMemcpyAsync(d.vb_pub.p, keys + stride * s.lo, stride * m, hipMemcpyHostToDevice, d.stream));
+    } else {
+      HIP_TRY(d.key_idx.ensure(4 * m + 64));
+      HIP_TRY(hipMemcpyAsync(d.key_idx.p, key_idx + s.lo, 4 * m, hipMemcpyHostToDevice, d.stream));
+    }
+    rc = verify_der_on_device(d, d.hashes.as<uint8_t>(), d.data.as<uint8_t>(), d.offsets.as<uint64_t>(),
+                              d.lengths.as<uint32_t>(), keys ? nullptr : d.key_idx.as<uint32_t>(),
+                              keys ? d.vb_pub.as<uint8_t>() : nullptr, key_format, m, d.bitmap.as<uint8_t>(), d.stream);
+    if (rc != PBFTV_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(out_bitmap + s.lo / 8, d.bitmap.p, (m + 7) / 8, hipMemcpyDeviceToHost, d.stream));
+    HIP_TRY(hipStreamSynchronize(d.stream));
+    return PBFTV_OK;
+    }();
+    if (rc != PBFTV_OK) (void)hipStreamSynchronize(d.stream);  // (fail() has kept the first error's message)
+    return rc;
+  });
+}
+
+int pbftv_ecdsa_p256_verify_der_batch(pbftv_ctx* ctx, const uint8_t* hashes, const uint8_t* der,
+                                      const uint64_t* der_off, const uint32_t* der_len, const uint32_t* key_idx,
+                                      uint64_t n, uint8_t* out_bitmap) {
+  if (!ctx) return fail(PBFTV_EINVAL, "ctx is null");
+  if (n >> 32) return fail(PBFTV_EINVAL, "n must be below 2^32");
+  if (n == 0) return PBFTV_OK;
+  if (!hashes || !der_off || !der_len || !key_idx || !out_bitmap) return fail(PBFTV_EINVAL, "null buffer");
+  for (auto& dp : ctx->devs)
+    if (!dp->have_keys) return fail(PBFTV_ENOKEYS, "pbftv_register_keys has not been called");
+  if (n <= ctx->wave_max.load(std::memory_order_relaxed)) {
+    // certificates and other small batches: the shared parser on the host,
+    // then the latency path exactly as for an r||s caller
+    std::vector<uint8_t> rs(64 * n);
+    if (pbftv_ecdsa_der_to_rs_batch(der, der_off, der_len, n, rs.data()) < 0)
+      return fail(PBFTV_EINVAL, "DER column: nonzero lengths with a null data pointer");
+    return pbftv_ecdsa_p256_verify_batch(ctx, hashes, rs.data(), key_idx, n, out_bitmap);
+  }
+  return verify_der_host_sharded(ctx, hashes, der, der_off, der_len, key_idx, nullptr, 0, n, out_bitmap);
+}
+
+int pbftv_ecdsa_p256_verify_wirekey_der_batch(pbftv_ctx* ctx, const uint8_t* hashes, const uint8_t* der,
+                                              const uint64_t* der_off, const uint32_t* der_len, const uint8_t* keys,
+                                              int key_format, uint64_t n, uint8_t* out_bitmap) {
+  if (!ctx) return fail(PBFTV_EINVAL, "ctx is null");
+  if (!pbftv_key_bytes(key_format)) return fail(PBFTV_EINVAL, "unknown key format");
+  if (n >> 32) return fail(PBFTV_EINVAL, "n must be below 2^32");
+  if (n == 0) return PBFTV_OK;
+  if (!hashes || !der_off || !der_len || !keys || !out_bitmap) return fail(PBFTV_EINVAL, "null buffer");
+  return verify_der_host_sharded(ctx, hashes, der, der_off, der_len, nullptr, keys, key_format, n, out_bitmap);
+}
+
 int pbftv_qc_stamps(pbftv_ctx* ctx, int dev, uint64_t out[8]) {
   Device* d = dev_of(ctx, dev);
   if (!d || !out) return fail(PBFTV_EINVAL, "bad context, device index or out pointer");
@@ -2902,14 +3147,32 @@ struct FlushSigner {
 
 static FlushSigner registered_signer(const uint32_t* key_idx) { return {key_idx, nullptr, 0, 0}; }
 
-// the argument checks the two kinds of signer differ in; PBFTV_OK: go on
-static int check_signer(const FlushSigner& by, uint64_t n, bool sig, const uint8_t* sig_rs) {
-  if (by.stride) {
-    if (n && sig && (!sig_rs || !by.given())) return fail(PBFTV_EINVAL, "signatures requested without sig_rs/keys");
-    if (sig && (n >> 32)) return fail(PBFTV_EINVAL, "n must be below 2^32");
-    return PBFTV_OK;
-  }
-  if (n && sig && (!sig_rs || !by.given())) return fail(PBFTV_EINVAL, "signatures requested without sig_rs/key_idx");
+// What a flush's signatures arrive as: the fixed r||s column (rs: 64 B each),
+// or ASN.1 DER as the messages carry them (a string column, the *_der
+// flushes), normalised on the device inside the same round trip.
+struct FlushSig {
+  const uint8_t* rs;
+  const uint8_t* der;
+  const uint64_t* der_off;
+  const uint32_t* der_len;
+  bool is_der;
+  bool given() const { return is_der ? der_off != nullptr && der_len != nullptr : rs != nullptr; }
+};
+
+static FlushSig rs_sigs(const uint8_t* sig_rs) { return {sig_rs, nullptr, nullptr, nullptr, false}; }
+static FlushSig der_sigs(const uint8_t* der, const uint64_t* off, const uint32_t* len) {
+  return {nullptr, der, off, len, true};
+}
+
+// the argument checks the kinds of signer and signature differ in; PBFTV_OK: go on
+static int check_signer(const FlushSigner& by, uint64_t n, bool sig, const FlushSig& sg) {
+  if (sg.is_der && (n >> 32)) return fail(PBFTV_EINVAL, "n must be below 2^32");
+  if (n && sig && (!sg.given() || !by.given()))
+    return fail(PBFTV_EINVAL, sg.is_der ? (by.stride ? "signatures requested without the DER column/keys"
+                                                     : "signatures requested without the DER column/key_idx")
+                                        : (by.stride ? "signatures requested without sig_rs/keys"
+                                                     : "signatures requested without sig_rs/key_idx"));
+  if (by.stride && sig && (n >> 32)) return fail(PBFTV_EINVAL, "n must be below 2^32");
   return PBFTV_OK;
 }
 
@@ -2918,27 +3181,49 @@ static size_t add_signer(Packer& p, const FlushSigner& by, uint64_t lo, uint64_t
   return by.stride ? p.add(by.keys + by.stride * lo, by.stride * m) : p.add(by.key_idx + lo, 4 * m);
 }
 
-// the signature stage of a flush on the digests in HBM (d.mu held)
-static int flush_verify(Device& d, const FlushSigner& by, size_t o_sig, size_t o_key, uint64_t m) {
+// ... and its signatures: the r||s rows, or the DER string column
+struct SigCols {
+  size_t rs;
+  Packer::Str der;
+};
+static SigCols add_sigs(Packer& p, const FlushSig& sg, uint64_t lo, uint64_t m) {
+  SigCols c{0, {0, 0, 0}};
+  if (sg.is_der) c.der = p.add_str(sg.der, sg.der_off, sg.der_len, lo, lo + m, pbftv::kDerMaxBytes);
+  else c.rs = p.add(sg.rs + 64 * lo, 64 * m);
+  return c;
+}
+
+// the signature stage of a flush on the digests in HBM (d.mu held): the r||s
+// column is the packed one, or the normaliser's output in the device's verify
+// scratch (d.stream: the scratch's lazy fence, no marker)
+static int flush_verify(Device& d, const FlushSigner& by, const FlushSig& sg, const SigCols& sc, size_t o_key,
+                        uint64_t m) {
   HIP_TRY(d.bitmap.ensure((m + 7) / 8 + 8));
+  if (sg.is_der) {
+    const pbftv::StrCol c = str_col(d, sc.der);
+    return verify_der_on_device(d, d.digests.as<uint8_t>(), c.data, c.off, c.len,
+                                by.stride ? nullptr : at<uint32_t>(d, o_key),
+                                by.stride ? at<uint8_t>(d, o_key) : nullptr, by.key_format, m,
+                                d.bitmap.as<uint8_t>(), d.stream);
+  }
   if (by.stride)
-    return varbase_on_device(d, d.digests.as<uint8_t>(), at<uint8_t>(d, o_sig), at<uint8_t>(d, o_key), by.key_format,
+    return varbase_on_device(d, d.digests.as<uint8_t>(), at<uint8_t>(d, sc.rs), at<uint8_t>(d, o_key), by.key_format,
                              m, d.bitmap.as<uint8_t>(), d.stream);
-  return verify_on_device(d, d.digests.as<uint8_t>(), at<uint8_t>(d, o_sig), at<uint32_t>(d, o_key), m,
+  return verify_on_device(d, d.digests.as<uint8_t>(), at<uint8_t>(d, sc.rs), at<uint32_t>(d, o_key), m,
                           d.bitmap.as<uint8_t>(), d.stream);
 }
 
 static int flush_requests_by(pbftv_ctx* ctx, uint64_t n, const int64_t* timestamps, const uint8_t* client_ids,
                              const uint64_t* client_id_off, const uint32_t* client_id_len, const uint8_t* operations,
                              const uint64_t* operation_off, const uint32_t* operation_len,
-                             const int64_t* sequence_ids, const uint8_t* sig_rs, const FlushSigner& by,
+                             const int64_t* sequence_ids, const FlushSig& sg, const FlushSigner& by,
                              const int64_t* assigned_seqs, uint8_t* out_digests, uint8_t* out_sig_bitmap,
                              uint8_t* out_consensus_digests) {
   if (!ctx) return fail(PBFTV_EINVAL, "ctx is null");
   if (n && (!timestamps || !client_id_off || !client_id_len || !operation_off || !operation_len || !sequence_ids))
     return fail(PBFTV_EINVAL, "null buffer");
   const bool sig = out_sig_bitmap != nullptr, two = out_consensus_digests != nullptr;
-  if (const int rc = check_signer(by, n, sig, sig_rs)) return rc;
+  if (const int rc = check_signer(by, n, sig, sg)) return rc;
   if (n && two && !assigned_seqs) return fail(PBFTV_EINVAL, "consensus digests requested without assigned_seqs");
   if (sig && !by.stride && !keys_ready(ctx)) return fail(PBFTV_ENOKEYS, "pbftv_register_keys has not been called");
   return run_sharded(ctx, n, [&](Device& d, Shard s) -> int {
@@ -2953,7 +3238,8 @@ static int flush_requests_by(pbftv_ctx* ctx, uint64_t n, const int64_t* timestam
     const size_t o_aseq = two ? p.add(assigned_seqs + s.lo, 8 * m) : 0;
     const auto cid = p.add_str(client_ids, client_id_off, client_id_len, s.lo, s.hi);
     const auto op = p.add_str(operations, operation_off, operation_len, s.lo, s.hi);
-    const size_t o_sig = sig ? p.add(sig_rs + 64 * s.lo, 64 * m) : 0, o_key = sig ? add_signer(p, by, s.lo, m) : 0;
+    const SigCols sigc = sig ? add_sigs(p, sg, s.lo, m) : SigCols{0, {0, 0, 0}};
+    const size_t o_key = sig ? add_signer(p, by, s.lo, m) : 0;
     std::lock_guard<std::mutex> lk(d.mu);
     HIP_TRY(hipSetDevice(d.id));
     int rc = upload(d, p);
@@ -2970,7 +3256,7 @@ static int flush_requests_by(pbftv_ctx* ctx, uint64_t n, const int64_t* timestam
     });
     if (rc != PBFTV_OK) return rc;
     if (sig) {
-      rc = flush_verify(d, by, o_sig, o_key, m);
+      rc = flush_verify(d, by, sg, sigc, o_key, m);
       if (rc != PBFTV_OK) return rc;
     }
     return results_out(d, s.lo, m, {{kDigests, d.digests.p, out_digests},
@@ -2985,8 +3271,19 @@ int pbftv_flush_requests(pbftv_ctx* ctx, uint64_t n, const int64_t* timestamps, 
                          const uint8_t* sig_rs, const uint32_t* key_idx, const int64_t* assigned_seqs,
                          uint8_t* out_digests, uint8_t* out_sig_bitmap, uint8_t* out_consensus_digests) {
   return flush_requests_by(ctx, n, timestamps, client_ids, client_id_off, client_id_len, operations, operation_off,
-                           operation_len, sequence_ids, sig_rs, registered_signer(key_idx), assigned_seqs,
+                           operation_len, sequence_ids, rs_sigs(sig_rs), registered_signer(key_idx), assigned_seqs,
                            out_digests, out_sig_bitmap, out_consensus_digests);
+}
+
+int pbftv_flush_requests_der(pbftv_ctx* ctx, uint64_t n, const int64_t* timestamps, const uint8_t* client_ids,
+                             const uint64_t* client_id_off, const uint32_t* client_id_len, const uint8_t* operations,
+                             const uint64_t* operation_off, const uint32_t* operation_len,
+                             const int64_t* sequence_ids, const uint8_t* der, const uint64_t* der_off,
+                             const uint32_t* der_len, const uint32_t* key_idx, const int64_t* assigned_seqs,
+                             uint8_t* out_digests, uint8_t* out_sig_bitmap, uint8_t* out_consensus_digests) {
+  return flush_requests_by(ctx, n, timestamps, client_ids, client_id_off, client_id_len, operations, operation_off,
+                           operation_len, sequence_ids, der_sigs(der, der_off, der_len), registered_signer(key_idx),
+                           assigned_seqs, out_digests, out_sig_bitmap, out_consensus_digests);
 }
 
 int pbftv_flush_requests_wirekey(pbftv_ctx* ctx, uint64_t n, const int64_t* timestamps, const uint8_t* client_ids,
@@ -2998,8 +3295,23 @@ int pbftv_flush_requests_wirekey(pbftv_ctx* ctx, uint64_t n, const int64_t* time
   const uint64_t stride = pbftv_key_bytes(key_format);
   if (!stride) return fail(PBFTV_EINVAL, "unknown key format");
   return flush_requests_by(ctx, n, timestamps, client_ids, client_id_off, client_id_len, operations, operation_off,
-                           operation_len, sequence_ids, sig_rs, FlushSigner{nullptr, keys, key_format, stride},
+                           operation_len, sequence_ids, rs_sigs(sig_rs), FlushSigner{nullptr, keys, key_format, stride},
                            assigned_seqs, out_digests, out_sig_bitmap, out_consensus_digests);
+}
+
+int pbftv_flush_requests_wirekey_der(pbftv_ctx* ctx, uint64_t n, const int64_t* timestamps, const uint8_t* client_ids,
+                                     const uint64_t* client_id_off, const uint32_t* client_id_len,
+                                     const uint8_t* operations, const uint64_t* operation_off,
+                                     const uint32_t* operation_len, const int64_t* sequence_ids, const uint8_t* der,
+                                     const uint64_t* der_off, const uint32_t* der_len, const uint8_t* keys,
+                                     int key_format, const int64_t* assigned_seqs, uint8_t* out_digests,
+                                     uint8_t* out_sig_bitmap, uint8_t* out_consensus_digests) {
+  const uint64_t stride = pbftv_key_bytes(key_format);
+  if (!stride) return fail(PBFTV_EINVAL, "unknown key format");
+  return flush_requests_by(ctx, n, timestamps, client_ids, client_id_off, client_id_len, operations, operation_off,
+                           operation_len, sequence_ids, der_sigs(der, der_off, der_len),
+                           FlushSigner{nullptr, keys, key_format, stride}, assigned_seqs, out_digests, out_sig_bitmap,
+                           out_consensus_digests);
 }
 
 int pbftv_digest_request_batch(pbftv_ctx* ctx, uint64_t n, const int64_t* timestamps, const uint8_t* client_ids,
@@ -3025,14 +3337,14 @@ static int flush_replies_by(pbftv_ctx* ctx, uint64_t n, const int64_t* view_ids,
                             const uint8_t* client_ids, const uint64_t* client_id_off, const uint32_t* client_id_len,
                             const uint8_t* node_ids, const uint64_t* node_id_off, const uint32_t* node_id_len,
                             const uint8_t* results, const uint64_t* result_off, const uint32_t* result_len,
-                            const uint8_t* sig_rs, const FlushSigner& by, uint8_t* out_digests,
+                            const FlushSig& sg, const FlushSigner& by, uint8_t* out_digests,
                             uint8_t* out_sig_bitmap) {
   if (!ctx) return fail(PBFTV_EINVAL, "ctx is null");
   if (n && (!view_ids || !timestamps || !client_id_off || !client_id_len || !node_id_off || !node_id_len ||
             !result_off || !result_len))
     return fail(PBFTV_EINVAL, "null buffer");
   const bool sig = out_sig_bitmap != nullptr;
-  if (const int rc = check_signer(by, n, sig, sig_rs)) return rc;
+  if (const int rc = check_signer(by, n, sig, sg)) return rc;
   if (sig && !by.stride && !keys_ready(ctx)) return fail(PBFTV_ENOKEYS, "pbftv_register_keys has not been called");
   return run_sharded(ctx, n, [&](Device& d, Shard s) -> int {
     const uint64_t m = s.hi - s.lo;
@@ -3045,7 +3357,8 @@ static int flush_replies_by(pbftv_ctx* ctx, uint64_t n, const int64_t* view_ids,
     const auto cid = p.add_str(client_ids, client_id_off, client_id_len, s.lo, s.hi);
     const auto nid = p.add_str(node_ids, node_id_off, node_id_len, s.lo, s.hi);
     const auto res = p.add_str(results, result_off, result_len, s.lo, s.hi);
-    const size_t o_sig = sig ? p.add(sig_rs + 64 * s.lo, 64 * m) : 0, o_key = sig ? add_signer(p, by, s.lo, m) : 0;
+    const SigCols sigc = sig ? add_sigs(p, sg, s.lo, m) : SigCols{0, {0, 0, 0}};
+    const size_t o_key = sig ? add_signer(p, by, s.lo, m) : 0;
     std::lock_guard<std::mutex> lk(d.mu);
     HIP_TRY(hipSetDevice(d.id));
     int rc = upload(d, p);
@@ -3058,7 +3371,7 @@ static int flush_replies_by(pbftv_ctx* ctx, uint64_t n, const int64_t* view_ids,
     });
     if (rc != PBFTV_OK) return rc;
     if (sig) {
-      rc = flush_verify(d, by, o_sig, o_key, m);
+      rc = flush_verify(d, by, sg, sigc, o_key, m);
       if (rc != PBFTV_OK) return rc;
     }
     return results_out(d, s.lo, m, {{kDigests, d.digests.p, out_digests},
@@ -3073,7 +3386,18 @@ int pbftv_flush_replies(pbftv_ctx* ctx, uint64_t n, const int64_t* view_ids, con
                         const uint8_t* sig_rs, const uint32_t* key_idx, uint8_t* out_digests,
                         uint8_t* out_sig_bitmap) {
   return flush_replies_by(ctx, n, view_ids, timestamps, client_ids, client_id_off, client_id_len, node_ids,
-                          node_id_off, node_id_len, results, result_off, result_len, sig_rs,
+                          node_id_off, node_id_len, results, result_off, result_len, rs_sigs(sig_rs),
+                          registered_signer(key_idx), out_digests, out_sig_bitmap);
+}
+
+int pbftv_flush_replies_der(pbftv_ctx* ctx, uint64_t n, const int64_t* view_ids, const int64_t* timestamps,
+                            const uint8_t* client_ids, const uint64_t* client_id_off, const uint32_t* client_id_len,
+                            const uint8_t* node_ids, const uint64_t* node_id_off, const uint32_t* node_id_len,
+                            const uint8_t* results, const uint64_t* result_off, const uint32_t* result_len,
+                            const uint8_t* der, const uint64_t* der_off, const uint32_t* der_len,
+                            const uint32_t* key_idx, uint8_t* out_digests, uint8_t* out_sig_bitmap) {
+  return flush_replies_by(ctx, n, view_ids, timestamps, client_ids, client_id_off, client_id_len, node_ids,
+                          node_id_off, node_id_len, results, result_off, result_len, der_sigs(der, der_off, der_len),
                           registered_signer(key_idx), out_digests, out_sig_bitmap);
 }
 
@@ -3086,7 +3410,21 @@ int pbftv_flush_replies_wirekey(pbftv_ctx* ctx, uint64_t n, const int64_t* view_
   const uint64_t stride = pbftv_key_bytes(key_format);
   if (!stride) return fail(PBFTV_EINVAL, "unknown key format");
   return flush_replies_by(ctx, n, view_ids, timestamps, client_ids, client_id_off, client_id_len, node_ids,
-                          node_id_off, node_id_len, results, result_off, result_len, sig_rs,
+                          node_id_off, node_id_len, results, result_off, result_len, rs_sigs(sig_rs),
+                          FlushSigner{nullptr, keys, key_format, stride}, out_digests, out_sig_bitmap);
+}
+
+int pbftv_flush_replies_wirekey_der(pbftv_ctx* ctx, uint64_t n, const int64_t* view_ids, const int64_t* timestamps,
+                                    const uint8_t* client_ids, const uint64_t* client_id_off,
+                                    const uint32_t* client_id_len, const uint8_t* node_ids,
+                                    const uint64_t* node_id_off, const uint32_t* node_id_len, const uint8_t* results,
+                                    const uint64_t* result_off, const uint32_t* result_len, const uint8_t* der,
+                                    const uint64_t* der_off, const uint32_t* der_len, const uint8_t* keys,
+                                    int key_format, uint8_t* out_digests, uint8_t* out_sig_bitmap) {
+  const uint64_t stride = pbftv_key_bytes(key_format);
+  if (!stride) return fail(PBFTV_EINVAL, "unknown key format");
+  return flush_replies_by(ctx, n, view_ids, timestamps, client_ids, client_id_off, client_id_len, node_ids,
+                          node_id_off, node_id_len, results, result_off, result_len, der_sigs(der, der_off, der_len),
                           FlushSigner{nullptr, keys, key_format, stride}, out_digests, out_sig_bitmap);
 }
 
@@ -3101,22 +3439,24 @@ int pbftv_digest_reply_batch(pbftv_ctx* ctx, uint64_t n, const int64_t* view_ids
                              nullptr);
 }
 
-int pbftv_flush_preprepares(pbftv_ctx* ctx, uint64_t n, const int64_t* view_ids, const int64_t* sequence_ids,
-                            const uint8_t* digests, const uint64_t* digest_off, const uint32_t* digest_len,
-                            const uint8_t* has_request, const int64_t* req_timestamps, const uint8_t* req_client_ids,
-                            const uint64_t* req_client_id_off, const uint32_t* req_client_id_len,
-                            const uint8_t* req_operations, const uint64_t* req_operation_off,
-                            const uint32_t* req_operation_len, const int64_t* req_sequence_ids, const uint8_t* sig_rs,
-                            const uint32_t* key_idx, uint32_t n_states, const int64_t* state_view_ids,
-                            const int64_t* state_last_seqs, const uint32_t* state_idx, uint8_t* out_digests,
-                            uint8_t* out_req_digests, uint8_t* out_sig_bitmap, uint8_t* out_msg_bitmap) {
+static int flush_preprepares_sig(pbftv_ctx* ctx, uint64_t n, const int64_t* view_ids, const int64_t* sequence_ids,
+                                 const uint8_t* digests, const uint64_t* digest_off, const uint32_t* digest_len,
+                                 const uint8_t* has_request, const int64_t* req_timestamps,
+                                 const uint8_t* req_client_ids, const uint64_t* req_client_id_off,
+                                 const uint32_t* req_client_id_len, const uint8_t* req_operations,
+                                 const uint64_t* req_operation_off, const uint32_t* req_operation_len,
+                                 const int64_t* req_sequence_ids, const FlushSig& sg, const uint32_t* key_idx,
+                                 uint32_t n_states, const int64_t* state_view_ids, const int64_t* state_last_seqs,
+                                 const uint32_t* state_idx, uint8_t* out_digests, uint8_t* out_req_digests,
+                                 uint8_t* out_sig_bitmap, uint8_t* out_msg_bitmap) {
   if (!ctx) return fail(PBFTV_EINVAL, "ctx is null");
+  const FlushSigner by = registered_signer(key_idx);
   if (n && (!view_ids || !sequence_ids || !digest_off || !digest_len || !has_request || !req_timestamps ||
             !req_client_id_off || !req_client_id_len || !req_operation_off || !req_operation_len ||
             !req_sequence_ids))
     return fail(PBFTV_EINVAL, "null buffer");
   const bool sig = out_sig_bitmap != nullptr, msg = out_msg_bitmap != nullptr;
-  if (n && sig && (!sig_rs || !key_idx)) return fail(PBFTV_EINVAL, "signatures requested without sig_rs/key_idx");
+  if (const int rc = check_signer(by, n, sig, sg)) return rc;
   if (n && msg && (!state_idx || (n_states && (!state_view_ids || !state_last_seqs))))
     return fail(PBFTV_EINVAL, "verifyMsg requested without states");
   if (sig && !keys_ready(ctx)) return fail(PBFTV_ENOKEYS, "pbftv_register_keys has not been called");
@@ -3147,7 +3487,8 @@ int pbftv_flush_preprepares(pbftv_ctx* ctx, uint64_t n, const int64_t* view_ids,
     const auto dg = p.add_str(digests, digest_off, digest_len, s.lo, s.hi);
     const auto cid = p.add_str(req_client_ids, req_client_id_off, req_client_id_len, s.lo, s.hi);
     const auto op = p.add_str(req_operations, req_operation_off, req_operation_len, s.lo, s.hi);
-    const size_t o_sig = sig ? p.add(sig_rs + 64 * s.lo, 64 * m) : 0, o_key = sig ? p.add(key_idx + s.lo, 4 * m) : 0;
+    const SigCols sigc = sig ? add_sigs(p, sg, s.lo, m) : SigCols{0, {0, 0, 0}};
+    const size_t o_key = sig ? add_signer(p, by, s.lo, m) : 0;
     size_t o_sv = 0, o_sl = 0, o_si = 0;
     if (msg) {
       o_sv = p.add(state_view_ids, 8ull * n_states);
@@ -3170,9 +3511,7 @@ int pbftv_flush_preprepares(pbftv_ctx* ctx, uint64_t n, const int64_t* view_ids,
     });
     if (rc != PBFTV_OK) return rc;
     if (sig) {
-      HIP_TRY(d.bitmap.ensure((m + 7) / 8 + 8));
-      rc = verify_on_device(d, d.digests.as<uint8_t>(), at<uint8_t>(d, o_sig), at<uint32_t>(d, o_key), m,
-                            d.bitmap.as<uint8_t>(), d.stream);
+      rc = flush_verify(d, by, sg, sigc, o_key, m);
       if (rc != PBFTV_OK) return rc;
     }
     uint8_t* msgok = nullptr;
@@ -3188,6 +3527,40 @@ int pbftv_flush_preprepares(pbftv_ctx* ctx, uint64_t n, const int64_t* view_ids,
                                     {kBitmap, d.bitmap.p, sig ? out_sig_bitmap : nullptr},
                                     {kByteFlags, msgok, out_msg_bitmap}});
   });
+}
+
+int pbftv_flush_preprepares(pbftv_ctx* ctx, uint64_t n, const int64_t* view_ids, const int64_t* sequence_ids,
+                            const uint8_t* digests, const uint64_t* digest_off, const uint32_t* digest_len,
+                            const uint8_t* has_request, const int64_t* req_timestamps, const uint8_t* req_client_ids,
+                            const uint64_t* req_client_id_off, const uint32_t* req_client_id_len,
+                            const uint8_t* req_operations, const uint64_t* req_operation_off,
+                            const uint32_t* req_operation_len, const int64_t* req_sequence_ids, const uint8_t* sig_rs,
+                            const uint32_t* key_idx, uint32_t n_states, const int64_t* state_view_ids,
+                            const int64_t* state_last_seqs, const uint32_t* state_idx, uint8_t* out_digests,
+                            uint8_t* out_req_digests, uint8_t* out_sig_bitmap, uint8_t* out_msg_bitmap) {
+  return flush_preprepares_sig(ctx, n, view_ids, sequence_ids, digests, digest_off, digest_len, has_request,
+                               req_timestamps, req_client_ids, req_client_id_off, req_client_id_len, req_operations,
+                               req_operation_off, req_operation_len, req_sequence_ids, rs_sigs(sig_rs), key_idx,
+                               n_states, state_view_ids, state_last_seqs, state_idx, out_digests, out_req_digests,
+                               out_sig_bitmap, out_msg_bitmap);
+}
+
+int pbftv_flush_preprepares_der(pbftv_ctx* ctx, uint64_t n, const int64_t* view_ids, const int64_t* sequence_ids,
+                                const uint8_t* digests, const uint64_t* digest_off, const uint32_t* digest_len,
+                                const uint8_t* has_request, const int64_t* req_timestamps,
+                                const uint8_t* req_client_ids, const uint64_t* req_client_id_off,
+                                const uint32_t* req_client_id_len, const uint8_t* req_operations,
+                                const uint64_t* req_operation_off, const uint32_t* req_operation_len,
+                                const int64_t* req_sequence_ids, const uint8_t* der, const uint64_t* der_off,
+                                const uint32_t* der_len, const uint32_t* key_idx, uint32_t n_states,
+                                const int64_t* state_view_ids, const int64_t* state_last_seqs,
+                                const uint32_t* state_idx, uint8_t* out_digests, uint8_t* out_req_digests,
+                                uint8_t* out_sig_bitmap, uint8_t* out_msg_bitmap) {
+  return flush_preprepares_sig(ctx, n, view_ids, sequence_ids, digests, digest_off, digest_len, has_request,
+                               req_timestamps, req_client_ids, req_client_id_off, req_client_id_len, req_operations,
+                               req_operation_off, req_operation_len, req_sequence_ids,
+                               der_sigs(der, der_off, der_len), key_idx, n_states, state_view_ids, state_last_seqs,
+                               state_idx, out_digests, out_req_digests, out_sig_bitmap, out_msg_bitmap);
 }
 
 int pbftv_digest_preprepare_batch(pbftv_ctx* ctx, uint64_t n, const int64_t* view_ids, const int64_t* sequence_ids,
@@ -3207,18 +3580,19 @@ int pbftv_digest_preprepare_batch(pbftv_ctx* ctx, uint64_t n, const int64_t* vie
 // Pool flush of a vote snapshot: Go-JSON + SHA-256 + verifyMsg + ECDSA in one
 // device round trip per shard (see pbftv.h).  Also the body of
 // pbftv_digest_vote_batch (no signatures, no states).
-int pbftv_flush_votes(pbftv_ctx* ctx, uint64_t n, const int64_t* view_ids, const int64_t* sequence_ids,
-                      const uint8_t* digests, const uint64_t* digest_off, const uint32_t* digest_len,
-                      const uint8_t* node_ids, const uint64_t* node_id_off, const uint32_t* node_id_len,
-                      const int64_t* msg_types, const uint8_t* sig_rs, const uint32_t* key_idx, uint32_t n_states,
-                      const int64_t* state_view_ids, const int64_t* state_last_seqs,
-                      const uint8_t* state_req_digests, const uint32_t* state_idx, uint8_t* out_digests,
-                      uint8_t* out_sig_bitmap, uint8_t* out_msg_bitmap) {
+static int flush_votes_sig(pbftv_ctx* ctx, uint64_t n, const int64_t* view_ids, const int64_t* sequence_ids,
+                           const uint8_t* digests, const uint64_t* digest_off, const uint32_t* digest_len,
+                           const uint8_t* node_ids, const uint64_t* node_id_off, const uint32_t* node_id_len,
+                           const int64_t* msg_types, const FlushSig& sg, const uint32_t* key_idx, uint32_t n_states,
+                           const int64_t* state_view_ids, const int64_t* state_last_seqs,
+                           const uint8_t* state_req_digests, const uint32_t* state_idx, uint8_t* out_digests,
+                           uint8_t* out_sig_bitmap, uint8_t* out_msg_bitmap) {
   if (!ctx) return fail(PBFTV_EINVAL, "ctx is null");
+  const FlushSigner by = registered_signer(key_idx);
   if (n && (!view_ids || !sequence_ids || !digest_off || !digest_len || !node_id_off || !node_id_len || !msg_types))
     return fail(PBFTV_EINVAL, "null buffer");
   const bool sig = out_sig_bitmap != nullptr, msg = out_msg_bitmap != nullptr;
-  if (n && sig && (!sig_rs || !key_idx)) return fail(PBFTV_EINVAL, "signatures requested without sig_rs/key_idx");
+  if (const int rc = check_signer(by, n, sig, sg)) return rc;
   if (n && msg && (!state_idx || (n_states && (!state_view_ids || !state_last_seqs || !state_req_digests))))
     return fail(PBFTV_EINVAL, "verifyMsg requested without states");
   if (sig && !keys_ready(ctx)) return fail(PBFTV_ENOKEYS, "pbftv_register_keys has not been called");
@@ -3233,10 +3607,11 @@ int pbftv_flush_votes(pbftv_ctx* ctx, uint64_t n, const int64_t* view_ids, const
                  o_type = p.add(msg_types + s.lo, 8 * m);
     const auto dg = p.add_str(digests, digest_off, digest_len, s.lo, s.hi);
     const auto nid = p.add_str(node_ids, node_id_off, node_id_len, s.lo, s.hi);
-    size_t o_sig = 0, o_key = 0, o_sv = 0, o_sl = 0, o_sd = 0, o_si = 0;
+    size_t o_key = 0, o_sv = 0, o_sl = 0, o_sd = 0, o_si = 0;
+    SigCols sigc{0, {0, 0, 0}};
     if (sig) {
-      o_sig = p.add(sig_rs + 64 * s.lo, 64 * m);
-      o_key = p.add(key_idx + s.lo, 4 * m);
+      sigc = add_sigs(p, sg, s.lo, m);
+      o_key = add_signer(p, by, s.lo, m);
     }
     if (msg) {
       o_sv = p.add(state_view_ids, 8ull * n_states);
@@ -3264,15 +3639,38 @@ int pbftv_flush_votes(pbftv_ctx* ctx, uint64_t n, const int64_t* view_ids, const
     });
     if (rc != PBFTV_OK) return rc;
     if (sig) {
-      HIP_TRY(d.bitmap.ensure((m + 7) / 8 + 8));
-      rc = verify_on_device(d, d.digests.as<uint8_t>(), at<uint8_t>(d, o_sig), at<uint32_t>(d, o_key), m,
-                            d.bitmap.as<uint8_t>(), d.stream);
+      rc = flush_verify(d, by, sg, sigc, o_key, m);
       if (rc != PBFTV_OK) return rc;
     }
     return results_out(d, s.lo, m, {{kDigests, d.digests.p, out_digests},
                                     {kBitmap, d.bitmap.p, sig ? out_sig_bitmap : nullptr},
                                     {kByteFlags, msgok, out_msg_bitmap}});
   });
+}
+
+int pbftv_flush_votes(pbftv_ctx* ctx, uint64_t n, const int64_t* view_ids, const int64_t* sequence_ids,
+                      const uint8_t* digests, const uint64_t* digest_off, const uint32_t* digest_len,
+                      const uint8_t* node_ids, const uint64_t* node_id_off, const uint32_t* node_id_len,
+                      const int64_t* msg_types, const uint8_t* sig_rs, const uint32_t* key_idx, uint32_t n_states,
+                      const int64_t* state_view_ids, const int64_t* state_last_seqs,
+                      const uint8_t* state_req_digests, const uint32_t* state_idx, uint8_t* out_digests,
+                      uint8_t* out_sig_bitmap, uint8_t* out_msg_bitmap) {
+  return flush_votes_sig(ctx, n, view_ids, sequence_ids, digests, digest_off, digest_len, node_ids, node_id_off,
+                         node_id_len, msg_types, rs_sigs(sig_rs), key_idx, n_states, state_view_ids, state_last_seqs,
+                         state_req_digests, state_idx, out_digests, out_sig_bitmap, out_msg_bitmap);
+}
+
+int pbftv_flush_votes_der(pbftv_ctx* ctx, uint64_t n, const int64_t* view_ids, const int64_t* sequence_ids,
+                          const uint8_t* digests, const uint64_t* digest_off, const uint32_t* digest_len,
+                          const uint8_t* node_ids, const uint64_t* node_id_off, const uint32_t* node_id_len,
+                          const int64_t* msg_types, const uint8_t* der, const uint64_t* der_off,
+                          const uint32_t* der_len, const uint32_t* key_idx, uint32_t n_states,
+                          const int64_t* state_view_ids, const int64_t* state_last_seqs,
+                          const uint8_t* state_req_digests, const uint32_t* state_idx, uint8_t* out_digests,
+                          uint8_t* out_sig_bitmap, uint8_t* out_msg_bitmap) {
+  return flush_votes_sig(ctx, n, view_ids, sequence_ids, digests, digest_off, digest_len, node_ids, node_id_off,
+                         node_id_len, msg_types, der_sigs(der, der_off, der_len), key_idx, n_states, state_view_ids,
+                         state_last_seqs, state_req_digests, state_idx, out_digests, out_sig_bitmap, out_msg_bitmap);
 }
 
 int pbftv_verify_msg_batch(int64_t state_view_id, int64_t state_last_seq, const uint8_t req_digest[32], uint64_t n,

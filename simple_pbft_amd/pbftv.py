@@ -76,6 +76,8 @@ def lib() -> ctypes.CDLL:
         "pbftv_set_kernel_timing": (ctypes.c_int, [_vp, ctypes.c_int]),
         "pbftv_kernel_time_ms": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double),
                                                 ctypes.POINTER(ctypes.c_uint64)]),
+        "pbftv_der_kernel_time_ms": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.POINTER(ctypes.c_double),
+                                                    ctypes.POINTER(ctypes.c_uint64)]),
         "pbftv_reset_kernel_times": (ctypes.c_int, [_vp]),
         "pbftv_qc_stamps": (ctypes.c_int, [_vp, ctypes.c_int, _vp]),
         "pbftv_set_latency_path_max": (ctypes.c_int, [_vp, ctypes.c_uint64]),
@@ -152,6 +154,24 @@ def lib() -> ctypes.CDLL:
                                          [_vp] * 4),
         "pbftv_flush_replies_wirekey": (ctypes.c_int, [_vp, ctypes.c_uint64] + [_vp] * 13 + [ctypes.c_int] +
                                         [_vp] * 2),
+        "pbftv_ecdsa_der_to_rs_batch_dev": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, _vp, ctypes.c_uint64, _vp, _vp,
+                                                           _vp]),
+        "pbftv_ecdsa_p256_verify_der_batch": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_uint64, _vp]),
+        "pbftv_ecdsa_p256_verify_der_batch_dev": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, _vp, _vp, _vp,
+                                                                 ctypes.c_uint64, _vp, _vp]),
+        "pbftv_ecdsa_p256_verify_wirekey_der_batch": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_int,
+                                                                     ctypes.c_uint64, _vp]),
+        "pbftv_ecdsa_p256_verify_wirekey_der_batch_dev": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, _vp, _vp, _vp,
+                                                                         ctypes.c_int, ctypes.c_uint64, _vp, _vp]),
+        "pbftv_flush_votes_der": (ctypes.c_int, [_vp, ctypes.c_uint64] + [_vp] * 13 + [ctypes.c_uint32] + [_vp] * 7),
+        "pbftv_flush_preprepares_der": (ctypes.c_int, [_vp, ctypes.c_uint64] + [_vp] * 18 + [ctypes.c_uint32] +
+                                        [_vp] * 7),
+        "pbftv_flush_requests_der": (ctypes.c_int, [_vp, ctypes.c_uint64] + [_vp] * 16),
+        "pbftv_flush_replies_der": (ctypes.c_int, [_vp, ctypes.c_uint64] + [_vp] * 17),
+        "pbftv_flush_requests_wirekey_der": (ctypes.c_int, [_vp, ctypes.c_uint64] + [_vp] * 12 + [ctypes.c_int] +
+                                             [_vp] * 4),
+        "pbftv_flush_replies_wirekey_der": (ctypes.c_int, [_vp, ctypes.c_uint64] + [_vp] * 15 + [ctypes.c_int] +
+                                            [_vp] * 2),
         "pbftv_qc_verify": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_uint64, ctypes.c_uint32, _vp,
                                            ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_int)]),
     }
@@ -336,6 +356,8 @@ K_ECDSA_COMB = 1
 K_SHA256 = 2
 K_ECDSA_WAVE = 3
 K_GOJSON = 4
+K_ECDSA_VARBASE = 5
+K_ECDSA_DER = 6  # (read through Verifier.der_kernel_time_ms; kernel_time_ms takes 0..5)
 
 
 class RequestColumns:
@@ -440,6 +462,40 @@ def _wirekey_inputs(n: int, sigs, keys, key_format: int, what: str):
     if sigs.shape != (n, 64) or keys.size != n * stride:
         raise ValueError(f"{what}: sigs must be (n, 64) uint8 and keys n * {stride} bytes")
     return sigs, keys, np.zeros((n + 7) // 8 + 1, np.uint8)
+
+
+class DerColumn:
+    """Signatures as ASN.1 DER (what Go's ecdsa.SignASN1 writes) for the *_der
+    calls: a string column -- blob, per-signature offsets (uint64) and lengths
+    (uint32).  Made from a list of encodings, or from the three arrays as they
+    are (any order, shared bytes, other bytes between the encodings)."""
+
+    def __init__(self, ders=None, blob=None, off=None, length=None):
+        if ders is not None:
+            blob, off, length = Verifier.pack([bytes(d) for d in ders])
+        self.blob = np.ascontiguousarray(blob, np.uint8)
+        self.off = np.ascontiguousarray(off, np.uint64)
+        self.len = np.ascontiguousarray(length, np.uint32)
+        self.n = len(self.len)
+        if self.off.shape != (self.n,):
+            raise ValueError("DerColumn: offsets and lengths must both be (n,)")
+
+    def args(self):
+        return [self.blob.ctypes.data, self.off.ctypes.data, self.len.ctypes.data]
+
+
+def _der_inputs(n: int, der, signer, what: str):
+    """(DerColumn | None, signer array | None, bitmap | None) of a *_der flush"""
+    if der is None:
+        return None, None, None
+    col = der if isinstance(der, DerColumn) else DerColumn(der)
+    if col.n != n:
+        raise ValueError(f"{what}: the DER column must hold n signatures")
+    return col, signer, np.zeros((n + 7) // 8 + 1, np.uint8)
+
+
+def _der_args(col):
+    return col.args() if col is not None else [None, None, None]
 
 
 def _states(n: int, states, state_idx, what: str, with_digests: bool):
@@ -595,6 +651,13 @@ class Verifier:
         ms = ctypes.c_double()
         cnt = ctypes.c_uint64()
         _check(self._L.pbftv_kernel_time_ms(self._h, dev, kernel, ctypes.byref(ms), ctypes.byref(cnt)))
+        return ms.value, cnt.value
+
+    def der_kernel_time_ms(self, dev: int):
+        """pbftv_der_kernel_time_ms: (ms, launches) of k_der_to_rs, timing id PBFTV_K_ECDSA_DER"""
+        ms = ctypes.c_double()
+        cnt = ctypes.c_uint64()
+        _check(self._L.pbftv_der_kernel_time_ms(self._h, dev, ctypes.byref(ms), ctypes.byref(cnt)))
         return ms.value, cnt.value
 
     def reset_kernel_times(self):
@@ -921,6 +984,154 @@ class Verifier:
                                  d_bitmap: int, stream: int | None = None):
         _check(self._L.pbftv_ecdsa_p256_verify_wirekey_batch_dev(self._h, dev, d_hashes, d_sigs, d_keys, key_format,
                                                                  n, d_bitmap, stream))
+
+    # ---- signatures as ASN.1 DER, parsed on the device
+    def der_to_rs_batch_dev(self, dev: int, d_data: int | None, d_offsets: int, d_lengths: int, n: int,
+                            d_out_rs: int, d_parsed_bitmap: int | None = None, stream: int | None = None):
+        """pbftv_ecdsa_der_to_rs_batch_dev: the normaliser alone, enqueued on stream."""
+        _check(self._L.pbftv_ecdsa_der_to_rs_batch_dev(self._h, dev, d_data, d_offsets, d_lengths, n, d_out_rs,
+                                                       d_parsed_bitmap, stream))
+
+    def verify_der_batch(self, hashes: np.ndarray, der, key_idx: np.ndarray) -> np.ndarray:
+        """pbftv_ecdsa_p256_verify_der_batch: verify_batch with the signatures as a
+        DerColumn (or a list of encodings); one that does not parse is a 0 bit."""
+        self._sync_env()
+        col = der if isinstance(der, DerColumn) else DerColumn(der)
+        hashes = np.ascontiguousarray(hashes, np.uint8).reshape(-1, 32)
+        key_idx = np.ascontiguousarray(key_idx, np.uint32)
+        n = hashes.shape[0]
+        assert col.n == n and key_idx.shape[0] == n
+        bm = np.zeros((n + 7) // 8 + 1, np.uint8)
+        _check(self._L.pbftv_ecdsa_p256_verify_der_batch(self._h, hashes.ctypes.data, *col.args(),
+                                                         key_idx.ctypes.data, n, bm.ctypes.data))
+        return bitmap_to_bool(bm, n)
+
+    def verify_der_batch_dev(self, dev: int, d_hashes: int, d_der: int | None, d_der_off: int, d_der_len: int,
+                             d_key_idx: int, n: int, d_bitmap: int, stream: int | None = None):
+        self._sync_env()
+        _check(self._L.pbftv_ecdsa_p256_verify_der_batch_dev(self._h, dev, d_hashes, d_der, d_der_off, d_der_len,
+                                                             d_key_idx, n, d_bitmap, stream))
+
+    def verify_wirekey_der_batch(self, hashes: np.ndarray, der, keys: np.ndarray, key_format: int) -> np.ndarray:
+        """pbftv_ecdsa_p256_verify_wirekey_der_batch: verify_wirekey_batch with the
+        signatures as a DerColumn (or a list of encodings)."""
+        stride = key_bytes(key_format)
+        if not stride:
+            raise ValueError(f"verify_wirekey_der_batch: unknown key format {key_format}")
+        col = der if isinstance(der, DerColumn) else DerColumn(der)
+        hashes = np.ascontiguousarray(hashes, np.uint8).reshape(-1, 32)
+        keys = np.ascontiguousarray(keys, np.uint8).reshape(-1, stride)
+        n = hashes.shape[0]
+        assert col.n == n and keys.shape[0] == n
+        bm = np.zeros((n + 7) // 8 + 1, np.uint8)
+        _check(self._L.pbftv_ecdsa_p256_verify_wirekey_der_batch(self._h, hashes.ctypes.data, *col.args(),
+                                                                 keys.ctypes.data, key_format, n, bm.ctypes.data))
+        return bitmap_to_bool(bm, n)
+
+    def verify_wirekey_der_batch_dev(self, dev: int, d_hashes: int, d_der: int | None, d_der_off: int,
+                                     d_der_len: int, d_keys: int, key_format: int, n: int, d_bitmap: int,
+                                     stream: int | None = None):
+        _check(self._L.pbftv_ecdsa_p256_verify_wirekey_der_batch_dev(self._h, dev, d_hashes, d_der, d_der_off,
+                                                                     d_der_len, d_keys, key_format, n, d_bitmap,
+                                                                     stream))
+
+    def flush_votes_der(self, cols: "VoteColumns", der=None, key_idx=None, states=None, state_idx=None,
+                        digests: bool = True):
+        """pbftv_flush_votes_der: flush_votes with the signatures as a DerColumn."""
+        self._sync_env()
+        n = cols.n
+        D, K, sbm = _der_inputs(n, der, key_idx, "flush_votes_der")
+        if K is not None:
+            K = np.ascontiguousarray(K, np.uint32)
+        out_d = np.zeros((max(n, 1), 32), np.uint8) if digests else None
+        k, sv, sl, sd, si, mbm = 0, None, None, None, None, None
+        if states is not None:
+            k, sv, sl, sd, si = _states(n, states, state_idx, "flush_votes_der", True)
+            mbm = np.zeros((n + 7) // 8 + 1, np.uint8)
+        _check(self._L.pbftv_flush_votes_der(self._h, n, *cols.args(), *_der_args(D), _ptr(K), k, _ptr(sv), _ptr(sl),
+                                             _ptr(sd), _ptr(si), _ptr(out_d), _ptr(sbm), _ptr(mbm)))
+        return (out_d[:n] if digests else None, bitmap_to_bool(sbm, n) if sbm is not None else None,
+                bitmap_to_bool(mbm, n) if mbm is not None else None)
+
+    def flush_requests_der(self, cols: "RequestColumns", der=None, key_idx=None, assigned_seqs=None,
+                           digests: bool = True):
+        """pbftv_flush_requests_der: (digests | None, sig_ok | None, consensus digests | None)."""
+        self._sync_env()
+        n = cols.n
+        D, K, sbm = _der_inputs(n, der, key_idx, "flush_requests_der")
+        if K is not None:
+            K = np.ascontiguousarray(K, np.uint32)
+        out_d = np.zeros((max(n, 1), 32), np.uint8) if digests else None
+        aseq = out_c = None
+        if assigned_seqs is not None:
+            aseq = np.ascontiguousarray(assigned_seqs, np.int64)
+            out_c = np.zeros((max(n, 1), 32), np.uint8)
+        _check(self._L.pbftv_flush_requests_der(self._h, n, *cols.args(), *_der_args(D), _ptr(K), _ptr(aseq),
+                                                _ptr(out_d), _ptr(sbm), _ptr(out_c)))
+        return (out_d[:n] if out_d is not None else None, bitmap_to_bool(sbm, n) if sbm is not None else None,
+                out_c[:n] if out_c is not None else None)
+
+    def flush_replies_der(self, cols: "ReplyColumns", der=None, key_idx=None, digests: bool = True):
+        """pbftv_flush_replies_der: (digests | None, sig_ok | None)."""
+        self._sync_env()
+        n = cols.n
+        D, K, sbm = _der_inputs(n, der, key_idx, "flush_replies_der")
+        if K is not None:
+            K = np.ascontiguousarray(K, np.uint32)
+        out_d = np.zeros((max(n, 1), 32), np.uint8) if digests else None
+        _check(self._L.pbftv_flush_replies_der(self._h, n, *cols.args(), *_der_args(D), _ptr(K), _ptr(out_d),
+                                               _ptr(sbm)))
+        return (out_d[:n] if out_d is not None else None, bitmap_to_bool(sbm, n) if sbm is not None else None)
+
+    def flush_requests_wirekey_der(self, cols: "RequestColumns", der=None, keys=None, key_format: int = KEY_XY,
+                                   assigned_seqs=None, digests: bool = True):
+        """pbftv_flush_requests_wirekey_der: (digests | None, sig_ok | None, consensus digests | None)."""
+        n = cols.n
+        D, K, sbm = _der_inputs(n, der, keys, "flush_requests_wirekey_der")
+        if K is not None:
+            K = np.ascontiguousarray(K, np.uint8)
+        out_d = np.zeros((max(n, 1), 32), np.uint8) if digests else None
+        aseq = out_c = None
+        if assigned_seqs is not None:
+            aseq = np.ascontiguousarray(assigned_seqs, np.int64)
+            out_c = np.zeros((max(n, 1), 32), np.uint8)
+        _check(self._L.pbftv_flush_requests_wirekey_der(self._h, n, *cols.args(), *_der_args(D), _ptr(K), key_format,
+                                                        _ptr(aseq), _ptr(out_d), _ptr(sbm), _ptr(out_c)))
+        return (out_d[:n] if out_d is not None else None, bitmap_to_bool(sbm, n) if sbm is not None else None,
+                out_c[:n] if out_c is not None else None)
+
+    def flush_replies_wirekey_der(self, cols: "ReplyColumns", der=None, keys=None, key_format: int = KEY_XY,
+                                  digests: bool = True):
+        """pbftv_flush_replies_wirekey_der: (digests | None, sig_ok | None)."""
+        n = cols.n
+        D, K, sbm = _der_inputs(n, der, keys, "flush_replies_wirekey_der")
+        if K is not None:
+            K = np.ascontiguousarray(K, np.uint8)
+        out_d = np.zeros((max(n, 1), 32), np.uint8) if digests else None
+        _check(self._L.pbftv_flush_replies_wirekey_der(self._h, n, *cols.args(), *_der_args(D), _ptr(K), key_format,
+                                                       _ptr(out_d), _ptr(sbm)))
+        return (out_d[:n] if out_d is not None else None, bitmap_to_bool(sbm, n) if sbm is not None else None)
+
+    def flush_preprepares_der(self, cols: "PrePrepareColumns", der=None, key_idx=None, states=None, state_idx=None,
+                              digests: bool = True, req_digests: bool = False):
+        """pbftv_flush_preprepares_der: (digests | None, request digests | None, sig_ok | None, msg_ok | None)."""
+        self._sync_env()
+        n = cols.n
+        D, K, sbm = _der_inputs(n, der, key_idx, "flush_preprepares_der")
+        if K is not None:
+            K = np.ascontiguousarray(K, np.uint32)
+        out_d = np.zeros((max(n, 1), 32), np.uint8) if digests else None
+        out_r = np.zeros((max(n, 1), 32), np.uint8) if req_digests else None
+        k, sv, sl, si, mbm = 0, None, None, None, None
+        if states is not None:
+            k, sv, sl, _, si = _states(n, states, state_idx, "flush_preprepares_der", False)
+            mbm = np.zeros((n + 7) // 8 + 1, np.uint8)
+        _check(self._L.pbftv_flush_preprepares_der(self._h, n, *cols.args(), *_der_args(D), _ptr(K), k, _ptr(sv),
+                                                   _ptr(sl), _ptr(si), _ptr(out_d), _ptr(out_r), _ptr(sbm),
+                                                   _ptr(mbm)))
+        return (out_d[:n] if out_d is not None else None, out_r[:n] if out_r is not None else None,
+                bitmap_to_bool(sbm, n) if sbm is not None else None,
+                bitmap_to_bool(mbm, n) if mbm is not None else None)
 
     def sha256_order_dev(self, dev: int, d_lengths: int, n: int, d_order: int, stream: int | None = None):
         _check(self._L.pbftv_sha256_order_dev(self._h, dev, d_lengths, n, d_order, stream))
