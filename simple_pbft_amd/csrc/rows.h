@@ -18,8 +18,14 @@
 // signed top limb, |value| < |a| |b| / 2^261 + p.  Inputs need
 // max|a_i| max|b_j| < 2^61 (each column then stays below 2^61.2).  Every limb
 // must also fit int32: X3 = R^2 - PPP - 2Q is renormalised (row_norm) before
-// Q - X3, and the fused check sums U1 + U2 + r ZZ12 instead of P + 2 U1 +
-// r ZZ12 (same value, limbs < 3 2^29 + 2^6).
+// Q - X3 (un-normalised, Q - X3 = 3Q + PPP - R^2 reaches 2^31 with three limbs
+// at their extremes at once).  The fused check's w = U1 + U2 + r ZZ12 has limbs
+// < 3 2^29 + 2^6; it is P + 2 U1 + r ZZ12 limb for limb (P = U2 - U1 in every
+// limb, and 32-bit sums wrap alike in any order), written with one addition
+// fewer, not a different bound.
+//
+// tests/rowfield.py restates this file limb for limb and asserts these
+// intervals; tests/test_gpu_field_probe.py compares every lane with it.
 #pragma once
 #include "fes.h"
 
@@ -202,7 +208,7 @@ __device__ __forceinline__ bool xyzz_add_check_rows(const RowCtx& c, bool& exc, 
   m = row_mul(c, sel4(c, P, R, rz, 0u), sel4(c, P, R, B.zz, 0u));
   gather4(g, m);  // PP, R^2, r ZZ1 ZZ2
   const uint32_t PP = g[0], R2 = g[1], rz12 = g[2];
-  const uint32_t w = U1 + U2 + rz12;  // = P + 2 U1 + r ZZ1 ZZ2; limbs < 3 (2^29 + 2^5)
+  const uint32_t w = U1 + U2 + rz12;  // = P + 2 U1 + r ZZ1 ZZ2, the same limbs; < 3 (2^29 + 2^5)
   m = row_mul(c, c.row & 1 ? P : PP, c.row & 1 ? rz12 : w);
   gather4(g, m);  // PP (P + 2 U1 + r ZZ12); P r ZZ1 ZZ2, zero iff either factor is (p prime)
   // both zero tests at once, half a wave each: lanes 0-31 the check's

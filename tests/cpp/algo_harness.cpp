@@ -12,6 +12,7 @@
 
 #include "../../simple_pbft_amd/csrc/p256_algo.h"
 #include "../../simple_pbft_amd/csrc/fes.h"
+#include "field_ops.h"
 
 using namespace pbftv;
 
@@ -333,3 +334,12 @@ int h_verify(const uint8_t* hash, const uint8_t* rs, const uint32_t* gtab, const
 }
 
 }  // extern "C"
+
+// ---- the wrappers of field_ops.h over n cases (hb_NAME): the CPU side of
+// tests/test_gpu_field_probe.py, which runs the same wrappers on the device ----
+#define FIELD_BATCH(name, IN, OUT)                                                          \
+  extern "C" void hb_##name(const uint32_t* in, uint32_t* out, int n) {                     \
+    for (int i = 0; i < n; ++i) field_ops::op_##name(in + (size_t)i * (IN), out + (size_t)i * (OUT)); \
+  }
+FIELD_OPS(FIELD_BATCH)
+extern "C" int hb_words(const char* name, int* in, int* out) { return field_op_words(name, in, out); }

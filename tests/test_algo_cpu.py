@@ -13,15 +13,14 @@ import numpy as np
 import pytest
 
 from conftest import crafted_exceptional, ROOT, fixture_arrays, oracle_sign_pool
+from rowfield_cases import (D_BOUND, L_BOUND, M29, M_BOUND, S_BOUND, limbs, rand_d, rand_l_type, rand_s,  # noqa: F401
+                            s_limbs_of, slimbs, sval, val)
 from safegcd_model import _N, _center, _divsteps30_var, _inv_wave, _shift30  # noqa: F401
 
 P = 0xFFFFFFFF00000001000000000000000000000000FFFFFFFFFFFFFFFFFFFFFFFF
 N = 0xFFFFFFFF00000000FFFFFFFFFFFFFFFFBCE6FAADA7179E84F3B9CAC2FC632551
 R = 1 << 261
-M29 = (1 << 29) - 1
 TABLE_WORDS = 33 * 128 * 16
-M_BOUND = int(1.172 * 2 ** 256)
-L_BOUND = int(2.344 * 2 ** 256)
 
 
 @pytest.fixture(scope="module")
@@ -29,27 +28,11 @@ def H():
     d = os.path.join(ROOT, "tests", "cpp")
     so = os.path.join(d, "libalgo_harness.so")
     src = os.path.join(d, "algo_harness.cpp")
-    hdrs = [os.path.join(ROOT, "simple_pbft_amd", "csrc", f) for f in ("fe29.h", "fes.h", "p256_algo.h", "p256_consts.h")]
+    hdrs = [os.path.join(ROOT, "simple_pbft_amd", "csrc", f) for f in ("fe29.h", "fes.h", "p256_algo.h", "p256_consts.h", "sec1.h", "safegcd.h")]
+    hdrs.append(os.path.join(d, "field_ops.h"))
     if not os.path.exists(so) or any(os.path.getmtime(h) > os.path.getmtime(so) for h in hdrs + [src]):
         subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", so, src], check=True)
     return ctypes.CDLL(so)
-
-
-def limbs(v):
-    return (ctypes.c_uint32 * 9)(*[(v >> (29 * i)) & M29 for i in range(9)])
-
-
-def val(l):
-    return sum(int(x) << (29 * i) for i, x in enumerate(l))
-
-
-def rand_l_type(rng):
-    """A lazily-added (L-type) input: limbs < 2^30, value < 2.344 * 2^256."""
-    while True:
-        l = [int(rng.choice([rng.integers(0, 1 << 30), (1 << 30) - 1, 0, 1 << 29])) for _ in range(9)]
-        l[8] = int(rng.integers(0, 1 << 26))
-        if val(l) < L_BOUND:
-            return (ctypes.c_uint32 * 9)(*l), val(l)
 
 
 def test_fe_mul_sqr_sub_bounds(H):
@@ -306,47 +289,6 @@ def test_xyzz_madd_chain_values_and_bounds(H):
 
 
 # ---- signed-limb arithmetic (simple_pbft_amd/csrc/fes.h, the comb's hot loop) ----
-S_BOUND = int(2 ** 257.5)
-D_BOUND = int(2 ** 258.5)
-
-
-def slimbs(l):
-    return (ctypes.c_uint32 * 9)(*[x & 0xFFFFFFFF for x in l])
-
-
-def sval(l):
-    """value of signed 32-bit limbs"""
-    return sum((int(x) - (1 << 32) if int(x) & 0x80000000 else int(x)) << (29 * i) for i, x in enumerate(l))
-
-
-def s_limbs_of(v):
-    """S-type limbs of a (possibly negative) value: limbs 0..7 in [0, 2^29), limb 8 the signed rest"""
-    l = [(v >> (29 * i)) & M29 for i in range(8)]
-    l.append(v >> 232)
-    return l
-
-
-def rand_s(rng, extreme=False):
-    if extreme:
-        v = int(rng.choice([S_BOUND - 1, -S_BOUND + 1, 0, P - 1, -(P - 1)]))
-        l = s_limbs_of(v)
-        if v > 0:
-            l[:8] = [M29] * 8 if rng.integers(0, 2) else l[:8]
-    else:
-        v = int.from_bytes(rng.bytes(33), "big") % (2 * S_BOUND) - S_BOUND
-        l = s_limbs_of(v)
-    while abs(sum(x << (29 * i) for i, x in enumerate(l))) >= S_BOUND:
-        l[8] -= 1 if l[8] > 0 else -1
-    return l, sum(x << (29 * i) for i, x in enumerate(l))
-
-
-def rand_d(rng, extreme=False):
-    a, va = rand_s(rng, extreme)
-    b, vb = rand_s(rng, extreme)
-    d = [x - y for x, y in zip(a, b)]
-    return d, va - vb
-
-
 def check_s(out):
     v = sval(out)
     assert all(0 <= int(x) < (1 << 29) for x in out[:8]), list(out)
