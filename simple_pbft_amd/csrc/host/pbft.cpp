@@ -7,6 +7,7 @@
 
 #include "../../../include/pbftv.h"
 #include "../gojson.h"
+#include "../tally.h"
 
 namespace pbft {
 
@@ -379,6 +380,36 @@ void Crypto::FlushVotes(const std::vector<VoteMsg>& votes, const std::vector<uin
   }
 }
 
+// FlushVotes, then the tally on the host: the matrix of first indices and the
+// per-state reduce of tally.h
+void Crypto::FlushVotesTally(const std::vector<VoteMsg>& votes, const std::vector<uint32_t>& key_idx,
+                             const std::vector<StateRef>& states, const std::vector<uint32_t>& state_idx,
+                             std::vector<bool>& sig_ok, std::vector<bool>& msg_ok, VoteTally& t) {
+  const size_t n = votes.size();
+  const uint32_t k = (uint32_t)states.size(), W = pbftv::tally_words(t.n_signers);
+  // a signer outside the universe never counts; the verify is not asked about it
+  std::vector<uint32_t> named(key_idx);
+  for (auto& x : named)
+    if (x >= t.n_signers) x = 0;
+  if (n) FlushVotes(votes, named, states, state_idx, sig_ok, msg_ok);
+  else sig_ok.clear(), msg_ok.clear();
+  std::vector<uint8_t> sbm((n + 7) / 8 + 1, 0), mbm((n + 7) / 8 + 1, 0);
+  for (size_t i = 0; i < n; ++i) {
+    if (key_idx[i] >= t.n_signers) sig_ok[i] = false;
+    sbm[i / 8] |= (uint8_t)(sig_ok[i] << (i % 8));
+    mbm[i / 8] |= (uint8_t)(msg_ok[i] << (i % 8));
+  }
+  std::vector<uint32_t> first((size_t)k * t.n_signers + 1, pbftv::kTallyNone);
+  pbftv::tally_first_host(sbm.data(), mbm.data(), key_idx.data(), state_idx.data(), n, 0, k, t.n_signers,
+                          first.data());
+  t.signers.resize((size_t)k * W, 0);
+  t.count.assign(k, 0);
+  t.quorum_at.assign(k, pbftv::kTallyNone);
+  for (uint32_t s = 0; s < k; ++s)
+    pbftv::tally_reduce_row(first.data() + (size_t)s * t.n_signers, t.n_signers, (uint32_t)n, t.quorum,
+                            t.signers.data() + (size_t)s * W, &t.count[s], &t.quorum_at[s]);
+}
+
 static Digest32 from_hex(const std::string& h) {
   Digest32 d{};
   auto nib = [](char c) { return (uint8_t)(c <= '9' ? c - '0' : c - 'a' + 10); };
@@ -405,6 +436,105 @@ ConsensusTable::FlushOutcome ConsensusTable::FlushPrepares(Crypto& c, const KeyT
 ConsensusTable::FlushOutcome ConsensusTable::FlushCommits(Crypto& c, const KeyTable& keys,
                                                           const std::vector<VoteMsg>& snapshot) {
   return flush(c, keys, snapshot, true);
+}
+
+ConsensusTable::FlushOutcome ConsensusTable::FlushPreparesTally(Crypto& c, const KeyTable& keys,
+                                                                const std::vector<VoteMsg>& snapshot) {
+  return flush_tally(c, keys, snapshot, false);
+}
+
+ConsensusTable::FlushOutcome ConsensusTable::FlushCommitsTally(Crypto& c, const KeyTable& keys,
+                                                               const std::vector<VoteMsg>& snapshot) {
+  return flush_tally(c, keys, snapshot, true);
+}
+
+// flush() with the quorum count taken from Crypto::FlushVotesTally: the stored
+// votes of each state go in as prior signer words, and what comes back says
+// which vote completed each state's quorum -- votes after it are not applied
+// (MSGENOUGH), votes up to it are stored as flush() stores them.
+ConsensusTable::FlushOutcome ConsensusTable::flush_tally(Crypto& c, const KeyTable& keys,
+                                                         const std::vector<VoteMsg>& snap, bool commit) {
+  const size_t n = snap.size();
+  const Stage takes = commit ? Stage::Prepared : Stage::PrePrepared;
+  Crypto::VoteTally t;
+  t.n_signers = keys.Count();
+  t.quorum = 2 * f;
+  const uint32_t W = pbftv::tally_words(t.n_signers);
+  std::map<int64_t, uint32_t> ref_of;
+  std::vector<Crypto::StateRef> refs;
+  std::vector<State*> ref_state;
+  std::vector<uint32_t> st_idx(n, UINT32_MAX), kidx(n, UINT32_MAX);  // (an unknown signer never counts)
+  for (size_t i = 0; i < n; ++i) {
+    auto it = states_.find(snap[i].SequenceID);
+    if (it != states_.end()) {
+      auto ins = ref_of.emplace(it->first, (uint32_t)refs.size());
+      if (ins.second) {
+        State& s = it->second;
+        refs.push_back({s.ViewID, s.LastSequenceID, from_hex(s.request_digest(c))});
+        ref_state.push_back(&s);
+        // its stored votes as prior signer words
+        t.signers.resize(refs.size() * (size_t)W, 0);
+        uint32_t* words = t.signers.data() + (refs.size() - 1) * (size_t)W;
+        const auto& stored = commit ? s.MsgLogs_.CommitMsgs : s.MsgLogs_.PrepareMsgs;
+        for (auto& kv : stored) {
+          const auto k = keys.Find(kv.first);
+          if (!k) return flush(c, keys, snap, commit);
+          words[*k / 32] |= 1u << (*k % 32);
+        }
+        if (s.CurrentStage == takes &&
+            (!s.MsgLogs_.ReqMsg || stored.size() >= (size_t)t.quorum || (commit && !s.prepared())))
+          return flush(c, keys, snap, commit);
+      }
+      st_idx[i] = ins.first->second;
+    }
+    if (auto k = keys.Find(snap[i].NodeID)) kidx[i] = *k;
+  }
+  FlushOutcome o;
+  o.accepted.assign(n, false);
+  o.applied.assign(n, false);
+  o.errors.assign(n, "");
+  std::vector<bool> sig_ok, msg_ok;
+  if (n) c.FlushVotesTally(snap, kidx, refs, st_idx, sig_ok, msg_ok, t);
+  const std::string what = commit ? "commit" : "prepare";
+  for (size_t i = 0; i < n; ++i) {
+    const bool m = st_idx[i] != UINT32_MAX && msg_ok[i];
+    const bool sg = kidx[i] != UINT32_MAX && sig_ok[i];
+    o.accepted[i] = m && sg;
+    if (!m) o.errors[i] = what + " message is corrupted";  // pbft_impl.go:117,147
+    else if (!sg) o.errors[i] = what + " message signature is invalid";
+    if (!o.accepted[i]) continue;
+    State& s = *ref_state[st_idx[i]];
+    const uint32_t at = t.quorum_at[st_idx[i]];
+    // (the state advances at vote `at` only, so up to there its stage is the one the flush began with)
+    if (s.CurrentStage != takes || (at != pbftv::kTallyNone && i > at)) continue;
+    o.applied[i] = true;
+    if (!commit) {
+      s.MsgLogs_.PrepareMsgs[snap[i].NodeID] = snap[i];
+      if (i == at) {
+        s.CurrentStage = Stage::Prepared;
+        VoteMsg v;
+        v.ViewID = s.ViewID;
+        v.SequenceID = snap[i].SequenceID;
+        v.Digest = snap[i].Digest;
+        v.Type = CommitMsg;
+        o.commits.push_back(v);
+      }
+    } else {
+      s.MsgLogs_.CommitMsgs[snap[i].NodeID] = snap[i];
+      if (i == at) {
+        s.CurrentStage = Stage::Committed;
+        s.LastSequenceID = snap[i].SequenceID;
+        last_committed_ = std::max(last_committed_, snap[i].SequenceID);
+        ReplyMsg r;
+        r.ViewID = s.ViewID;
+        r.Timestamp = s.MsgLogs_.ReqMsg->Timestamp;
+        r.ClientID = s.MsgLogs_.ReqMsg->ClientID;
+        r.Result = "Executed";
+        o.replies.emplace_back(r, *s.MsgLogs_.ReqMsg);
+      }
+    }
+  }
+  return o;
 }
 
 ConsensusTable::FlushOutcome ConsensusTable::flush(Crypto& c, const KeyTable& keys, const std::vector<VoteMsg>& snap,

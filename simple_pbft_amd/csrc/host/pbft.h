@@ -107,6 +107,19 @@ class Crypto {
   virtual void FlushVotes(const std::vector<VoteMsg>& votes, const std::vector<uint32_t>& key_idx,
                           const std::vector<StateRef>& states, const std::vector<uint32_t>& state_idx,
                           std::vector<bool>& sig_ok, std::vector<bool>& msg_ok);
+  // FlushVotes plus the quorum tally of the snapshot (csrc/tally.h): a vote counts iff both its bits are set, its state is in
+  // range and key_idx[j] < n_signers.  signers: the states' prior signer words
+  // in (states.size() * ceil(n_signers / 32), bit k = key index k), the unions
+  // out; count and quorum_at per state (pbftv::kTallyNone / kTallyBefore or the index
+  // of the vote that completed the quorum).  It runs FlushVotes -- with
+  // GpuCrypto one device round trip -- and then the reduce on the host.
+  struct VoteTally {
+    uint32_t n_signers = 0, quorum = 0;
+    std::vector<uint32_t> signers, count, quorum_at;
+  };
+  virtual void FlushVotesTally(const std::vector<VoteMsg>& votes, const std::vector<uint32_t>& key_idx,
+                               const std::vector<StateRef>& states, const std::vector<uint32_t>& state_idx,
+                               std::vector<bool>& sig_ok, std::vector<bool>& msg_ok, VoteTally& tally);
 };
 
 class GpuCrypto : public Crypto {
@@ -140,6 +153,12 @@ class KeyTable {
     auto it = idx_.find(id);
     if (it == idx_.end()) return std::nullopt;
     return it->second;
+  }
+  // one past the largest index: the signer universe of a tally (the registered key count)
+  uint32_t Count() const {
+    uint32_t c = 0;
+    for (auto& kv : idx_) c = kv.second + 1 > c ? kv.second + 1 : c;
+    return c;
   }
 
  private:
@@ -239,8 +258,18 @@ class ConsensusTable {
   };
   FlushOutcome FlushPrepares(Crypto& c, const KeyTable& keys, const std::vector<VoteMsg>& snapshot);
   FlushOutcome FlushCommits(Crypto& c, const KeyTable& keys, const std::vector<VoteMsg>& snapshot);
+  // The same flushes with the quorum count done by Crypto::FlushVotesTally:
+  // no per-vote quorum test over every state's map -- only
+  // the votes up to each state's quorum index are stored, and the state
+  // advances at that index.  Same outcome and same stored votes as the two
+  // above.  (A state whose stored votes cannot be named as key indices, or
+  // that already holds a quorum without having advanced, is a case the tally
+  // does not describe: the call then takes the path above.)
+  FlushOutcome FlushPreparesTally(Crypto& c, const KeyTable& keys, const std::vector<VoteMsg>& snapshot);
+  FlushOutcome FlushCommitsTally(Crypto& c, const KeyTable& keys, const std::vector<VoteMsg>& snapshot);
 
  private:
+  FlushOutcome flush_tally(Crypto& c, const KeyTable& keys, const std::vector<VoteMsg>& snap, bool commit);
   FlushOutcome flush(Crypto& c, const KeyTable& keys, const std::vector<VoteMsg>& snap, bool commit);
   int64_t view_;
   int64_t last_committed_ = -1;
