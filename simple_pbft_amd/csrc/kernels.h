@@ -4,6 +4,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "qc_mail.h"
+
 namespace pbftv {
 
 // ---- ECDSA-P256 (p256_kernels.hip) ----
@@ -123,51 +125,7 @@ uint64_t wave_path_max();
 // (the host reruns the certificate with a launch).  Counted by pbftv_qc_counters.
 constexpr int kRowsExact = 4;
 
-// The latency path's mailbox in pinned coherent host memory: a 64-B header,
-// then the inputs of up to cap signatures (hashes cap*32, r||s cap*64, key
-// indices cap*4) and one result byte per signature.  The host writes the
-// inputs, n and then bell = the request's sequence number; an armed kernel
-// (k_ecdsa_wave_armed) waiting for that number serves it; stop = seq cancels
-// the armed kernel, which then reports expired = seq (verify_kernels.h); so
-// does any change of halt (a disarm, or the process-wide quiesce of a GPU,
-// pbftv_api.cpp).  Two armed kernels can be resident at once (a rotation's
-// successor beside its predecessor, one per armed stream), so each armed
-// stream slot has its OWN expired word and its own live words (each wave's
-// first request number once it is resident): two kernels leaving at once
-// (a halt bump) cannot overwrite each other's report.
-// The first kQcSlots signatures are also written to their own 3-line slot
-// (slot_off): line 0 = {tag, n, key, 0, hash[32], 0, 0, 0, tag}, line 1 =
-// {tag, 0, 0, 0, r[32], 0, 0, 0, tag}, line 2 likewise with s; the tags (the
-// request number) are written after their line's data, the last dword first.
-struct QcMail {
-  uint32_t bell, n, stop, expired_s0, cap, halt, expired_s1, pad[9];  // (stop at dword 2, halt at 5: read by the kernel)
-  static constexpr uint32_t kQcSlots = 8;
-  static constexpr uint32_t kQcCap = 128;  // signatures per call up to which the mailbox is laid out at cap = 128
-  static constexpr int kArmSlots = 2;      // armed stream slots (pbftv_api.cpp Device::qstream)
-  // the expired word of armed stream slot s
-  __host__ __device__ uint32_t* expired(int s) { return s ? &expired_s1 : &expired_s0; }
-  static constexpr size_t slot_off(uint32_t i) { return 64 + 192 * (size_t)i; }
-  // each armed wave's first request number once it is resident (4 B per
-  // wave), per armed stream slot
-  static constexpr size_t live_off(int s = 0) { return 64 + 192 * (size_t)kQcSlots + 4 * (size_t)kQcCap * s; }
-  // one verdict byte per signature, right after the live words: with the
-  // header and the slot lines in the mailbox's FIRST 4-KiB page, so a
-  // certificate of <= kQcSlots touches one page of it (one TLB entry on the
-  // host, one translation on the GPU, both warm from the polling)
-  static constexpr size_t res_off(uint32_t = kQcCap) { return live_off(kArmSlots); }
-  // the input arrays of signatures kQcSlots.. (and of every signature on the
-  // launched path), after cap verdict bytes
-  static constexpr size_t arrays_off(uint32_t cap = kQcCap) {
-    return (res_off() + (cap > kQcCap ? cap : kQcCap) + 63) & ~(size_t)63;
-  }
-  static constexpr size_t hashes_off(uint32_t cap = kQcCap) { return arrays_off(cap); }
-  static constexpr size_t sigs_off(uint32_t cap) { return arrays_off(cap) + 32 * (size_t)cap; }
-  static constexpr size_t keys_off(uint32_t cap) { return arrays_off(cap) + 96 * (size_t)cap; }
-  // diagnostics: per armed wave (slots and helpers), its {wall clock, shader
-  // clock} when it saw its request and when it wrote its verdict (pbftv_qc_stamps)
-  static constexpr size_t stamps_off(uint32_t cap) { return (keys_off(cap) + 4 * (size_t)cap + 63) & ~(size_t)63; }
-  static constexpr size_t bytes(uint32_t cap) { return stamps_off(cap) + 32 * (size_t)kQcCap + 64; }
-};
+// The latency path's mailbox (QcMail) and its protocol: qc_mail.h
 struct ArmArgs {
   QcMail* mail;
   uint32_t want;       // the request sequence number this launch serves

@@ -919,13 +919,18 @@ hipError_t qc_rotate(Device& d) {
   return hipSuccess;
 }
 
+// how many of the armed kernel's first w workgroups are resident (their live words)
+uint32_t qc_live_count(Device& d, uint32_t w) {
+  const uint32_t* live = reinterpret_cast<const uint32_t*>(d.stage.as<uint8_t>() + QcMail::live_off(d.arm_stream));
+  uint32_t k = 0;
+  for (uint32_t i = 0; i < w; ++i) k += __atomic_load_n(live + i, __ATOMIC_ACQUIRE) == d.armed_first;
+  return k;
+}
+
 // every workgroup of the armed kernel resident (checked once per arming)
 bool qc_all_live(Device& d) {
   if (d.arm_live) return true;
-  if (!d.arm_seq) return false;
-  const uint32_t* live = reinterpret_cast<const uint32_t*>(d.stage.as<uint8_t>() + QcMail::live_off(d.arm_stream));
-  for (uint32_t w = 0; w < d.arm_waves; ++w)
-    if (__atomic_load_n(live + w, __ATOMIC_ACQUIRE) != d.armed_first) return false;
+  if (!d.arm_seq || qc_live_count(d, d.arm_waves) != d.arm_waves) return false;
   d.arm_live = true;
   return true;
 }
@@ -937,9 +942,8 @@ bool qc_all_live(Device& d) {
 // certificate is launched, qc_all_live)
 void qc_retire(Device& d) {
   if (!d.retiring || !d.arm_seq) return;
-  const uint32_t* live = reinterpret_cast<const uint32_t*>(d.stage.as<uint8_t>() + QcMail::live_off(d.arm_stream));
-  for (uint32_t w = 0; w < std::min<uint32_t>(d.arm_waves, QcMail::kQcSlots); ++w)
-    if (__atomic_load_n(live + w, __ATOMIC_ACQUIRE) != d.armed_first) return;  // not every slot resident yet
+  const uint32_t w = std::min<uint32_t>(d.arm_waves, QcMail::kQcSlots);
+  if (qc_live_count(d, w) != w) return;  // not every slot resident yet
   __atomic_store_n(&qc_mail(d)->stop, d.retiring, __ATOMIC_RELEASE);
   d.retiring = 0;
 }
@@ -2470,9 +2474,7 @@ int pbftv_ecdsa_p256_verify_batch(pbftv_ctx* ctx, const uint8_t* hashes, const u
       uint8_t* const hp = st8 + QcMail::hashes_off(cap) + 32 * lo;
       uint8_t* const sp = st8 + QcMail::sigs_off(cap) + 64 * lo;
       uint32_t* const kp = reinterpret_cast<uint32_t*>(st8 + QcMail::keys_off(cap)) + lo;
-      std::memcpy(hp, hashes + 32 * lo, 32 * (n - lo));
-      std::memcpy(sp, sig_rs + 64 * lo, 64 * (n - lo));
-      std::memcpy(kp, key_idx + lo, 4 * (n - lo));
+      pbftv::qc_write_arrays(st8, cap, hashes, sig_rs, key_idx, lo, n);
       HIP_TRY(set_dev());
       HIP_TRY(latency_stream(d, &lst));
       // beside this device's lane batches: one wave per signature (a row
@@ -2497,11 +2499,8 @@ int pbftv_ecdsa_p256_verify_batch(pbftv_ctx* ctx, const uint8_t* hashes, const u
     }
     const bool trace_qc = trace_qc_enabled();
     if (trace_qc && small && d.arm_seq && n <= d.arm_waves && n > QcMail::kQcSlots && !qc_all_live(d)) {
-      const uint32_t* lv = reinterpret_cast<const uint32_t*>(d.stage.as<uint8_t>() + QcMail::live_off(d.arm_stream));
-      uint32_t k = 0;
-      for (uint32_t w = 0; w < d.arm_waves; ++w) k += __atomic_load_n(lv + w, __ATOMIC_ACQUIRE) == d.armed_first;
       fprintf(stderr, "pbftv[dev %d] qc n=%llu launched: %u of %u workgroups of armed %u live (armed %.1f ms ago, retiring %u)\n",
-              d.id, (unsigned long long)n, k, d.arm_waves, d.arm_seq.load(),
+              d.id, (unsigned long long)n, qc_live_count(d, d.arm_waves), d.arm_waves, d.arm_seq.load(),
               std::chrono::duration<double, std::milli>(h_in - d.armed_at).count(), d.retiring);
     }
     if (trace_qc && small && !(d.arm_seq && n <= d.arm_waves))  // (diagnostics: why a launch)
@@ -2521,37 +2520,13 @@ int pbftv_ecdsa_p256_verify_batch(pbftv_ctx* ctx, const uint8_t* hashes, const u
     if (d.arm_seq && (split || (n <= d.arm_waves && (n <= QcMail::kQcSlots || qc_all_live(d))))) {
       cur = d.arm_seq;
       const uint64_t na = split ? std::min<uint64_t>(n, d.arm_waves) : n;  // signatures the armed kernel serves
-      if (n > QcMail::kQcSlots && !split) {  // the helpers' inputs (slots kQcSlots..n-1), before any slot tag
-        std::memcpy(st8 + QcMail::hashes_off(cap) + 32 * QcMail::kQcSlots, hashes + 32 * QcMail::kQcSlots,
-                    32 * (n - QcMail::kQcSlots));
-        std::memcpy(st8 + QcMail::sigs_off(cap) + 64 * QcMail::kQcSlots, sig_rs + 64 * QcMail::kQcSlots,
-                    64 * (n - QcMail::kQcSlots));
-        std::memcpy(st8 + QcMail::keys_off(cap) + 4 * QcMail::kQcSlots, key_idx + QcMail::kQcSlots,
-                    4 * (n - QcMail::kQcSlots));
-      }
+      // The helpers' inputs (signatures kQcSlots..n-1) go in before any slot
+      // tag of qc_post: a helper reads them as soon as wave 0 has seen line 0
+      // of its slot and relayed the request.
+      if (n > QcMail::kQcSlots && !split) pbftv::qc_write_arrays(st8, cap, hashes, sig_rs, key_idx, QcMail::kQcSlots, n);
       // the kernel waits for cur + 1 next (0 is "none": cancel it at the wrap)
       d.arm_seq = d.seq_counter = cur + 1;
-      // the slots: each line's data, then its tags (a line is read by the GPU
-      // as one snapshot, and x86 stores become visible in order)
-      for (uint32_t i = 0; i < QcMail::kQcSlots; ++i) {
-        uint32_t* l0 = reinterpret_cast<uint32_t*>(st8 + QcMail::slot_off(i));
-        uint32_t* l1 = l0 + 16;
-        uint32_t* l2 = l0 + 32;
-        if (i < na) {
-          std::memcpy(l0 + 4, hashes + 32 * i, 32);
-          std::memcpy(l1 + 4, sig_rs + 64 * i, 32);
-          std::memcpy(l2 + 4, sig_rs + 64 * i + 32, 32);
-          l0[2] = key_idx[i];
-          for (uint32_t* l : {l1, l2}) {
-            __atomic_store_n(l + 15, cur, __ATOMIC_RELEASE);
-            __atomic_store_n(l, cur, __ATOMIC_RELEASE);
-          }
-        }
-        l0[1] = (uint32_t)na;  // a slot past na: line 0 only (its wave reads na and waits for the next)
-        __atomic_store_n(l0 + 15, cur, __ATOMIC_RELEASE);
-        __atomic_store_n(l0, cur, __ATOMIC_RELEASE);
-      }
-      __atomic_store_n(&m->bell, cur, __ATOMIC_RELEASE);  // inputs and n are in: ring
+      pbftv::qc_post(st8, cur, (uint32_t)na, hashes, sig_rs, key_idx);
       if (na < n) {  // (split) the rest in one launch, beside the armed slots
         int rc = launch_range(na);
         if (rc != PBFTV_OK) return rc;

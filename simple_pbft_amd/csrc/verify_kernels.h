@@ -1586,182 +1586,182 @@ __global__ void __launch_bounds__(64 * kRowWaves) k_ecdsa_rows(const uint8_t* __
 // keeps one armed per device), so neither a launch nor a re-arm is on a
 // certificate's critical path: after request `want` it waits for want + 1.
 // One wave per signature slot (QcMail::kQcSlots = 8: a certificate of
-// n = 3f+1 <= 9 replicas).  Each wave polls, in ONE wave-wide load (lane l
-// reads dword l % 16 of line l / 16), the three 64-B lines of its slot and the
-// mailbox header: every slot line carries the request number in its first and
-// last dword, written by the host after the line's data (one line is read as
-// one snapshot of the host's cache line, and x86 stores become visible in
-// order; requiring both tags also covers a read that tore a line in two), so
-// three matching lines mean n, the key and the hash / r / s are already in
-// registers -- no second PCIe round trip.  Waves with slots >= n need only
-// line 0 (n) and go straight back to waiting.  Every wave reaches an exit: a cancel (header stop == the
-// request number it waits for, or a change of the header's halt word) or the
-// budget (wall-clock ticks since launch); a wave that leaves writes
-// expired = that number, and the host serves a request that raced the exit
-// with a launch instead.  Waits are s_sleep between polls (spin: see
-// ArmArgs); host words are read with system-scope loads; nothing is written
-// through the scalar cache.  The key tables' pointers and validity flags of
-// the first 128 keys are loaded once, at launch (a key change cancels first).
-// key data of key k: from the per-lane prefetch for k < 128, else from memory
-__device__ __forceinline__ void armed_key(uint32_t k, uint32_t nkeys, const uint4* qt_lo, const uint4* qt_hi,
-                                          uint32_t kv_lo, uint32_t kv_hi, const uint32_t* __restrict__ key_valid,
-                                          const uint4* const* __restrict__ qtabs, bool& key_ok, const uint4*& qtab) {
-  if (k < 128 && k < nkeys) {  // prefetched
-    const int kl = (int)(k & 63);
-    const uint64_t ql = (uint64_t)(uintptr_t)(k < 64 ? qt_lo : qt_hi);
-    const uint32_t lo = __builtin_amdgcn_readlane((uint32_t)ql, kl),
-                   hi = __builtin_amdgcn_readlane((uint32_t)(ql >> 32), kl);
-    qtab = reinterpret_cast<const uint4*>((uintptr_t)(((uint64_t)hi << 32) | lo));
-    key_ok = __builtin_amdgcn_readlane(k < 64 ? kv_lo : kv_hi, kl) != 0;
-  } else {
-    key_ok = k < nkeys && key_valid[k] != 0;
-    qtab = qtabs[k < nkeys ? k : 0];
+// n = 3f+1 <= 9 replicas).  Each wave polls, in ONE wave-wide load, the lines
+// of its slot and the mailbox header (qc_mail.h: the format, and the reader
+// used here over a WaveSnap), so a ready slot means n, the key and the
+// hash / r / s are already in registers -- no second PCIe round trip.  Waves
+// with slots >= n go straight back to waiting.  Every wave reaches an exit: a
+// cancel (qc_cancelled) or the budget (wall-clock ticks since launch); a wave
+// that leaves writes expired = the number it waited for, and the host serves a
+// request that raced the exit with a launch instead.  Waits are s_sleep
+// between polls (spin: see ArmArgs); host words are read with system-scope
+// loads; nothing is written through the scalar cache.  The key tables'
+// pointers and validity flags of the first 128 keys are loaded once, at launch
+// (a key change cancels first).
+
+// the dword each lane of a wave loaded
+struct WaveSnap {
+  uint32_t v;
+  __device__ __forceinline__ uint32_t operator[](int lane) const { return __builtin_amdgcn_readlane(v, lane); }
+};
+// ... from the mailbox: each lane the dword at its byte offset `off`
+__device__ __forceinline__ WaveSnap armed_load(const ArmArgs& a, size_t off) {
+  return {__hip_atomic_load(reinterpret_cast<const uint32_t*>(reinterpret_cast<const uint8_t*>(a.mail) + off),
+                            __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM)};
+}
+
+// key data for keys < 128, two per lane (lane l: keys l and l + 64), prefetched at launch
+struct ArmedKeys {
+  const uint4* qt_lo = nullptr;
+  const uint4* qt_hi = nullptr;
+  uint32_t kv_lo = 0, kv_hi = 0;
+  __device__ __forceinline__ void load(const ArmArgs& a, uint32_t lane) {
+    const uint4* const* qtabs = reinterpret_cast<const uint4* const*>(a.qtabs);
+    qt_lo = lane < a.nkeys ? qtabs[lane] : nullptr;
+    qt_hi = lane + 64 < a.nkeys ? qtabs[lane + 64] : nullptr;
+    kv_lo = lane < a.nkeys ? a.key_valid[lane] : 0u;
+    kv_hi = lane + 64 < a.nkeys ? a.key_valid[lane + 64] : 0u;
   }
+  // key data of key k: from the prefetch for k < 128, else from memory
+  __device__ __forceinline__ void lookup(const ArmArgs& a, uint32_t k, bool& key_ok, const uint4*& qtab) const {
+    if (k < 128 && k < a.nkeys) {
+      const int kl = (int)(k & 63);
+      const uint64_t ql = (uint64_t)(uintptr_t)(k < 64 ? qt_lo : qt_hi);
+      const uint32_t lo = __builtin_amdgcn_readlane((uint32_t)ql, kl),
+                     hi = __builtin_amdgcn_readlane((uint32_t)(ql >> 32), kl);
+      qtab = reinterpret_cast<const uint4*>((uintptr_t)(((uint64_t)hi << 32) | lo));
+      key_ok = __builtin_amdgcn_readlane(k < 64 ? kv_lo : kv_hi, kl) != 0;
+    } else {
+      key_ok = k < a.nkeys && a.key_valid[k] != 0;
+      qtab = reinterpret_cast<const uint4* const*>(a.qtabs)[k < a.nkeys ? k : 0];
+    }
+  }
+};
+
+// The pieces of an armed server's wave (no barrier in any of them: the row
+// kernel calls them in its wave 0 only).
+// A slot wave's wait for request `want` (`off`: its lane's qc_poll_off): true
+// with the ready slot in v, or false at a cancel or the budget.
+__device__ __forceinline__ bool armed_wait_slot(const ArmArgs& a, uint32_t b, uint32_t lane, size_t off, uint32_t want,
+                                                uint64_t t0, WaveSnap& v) {
+  for (;;) {
+    v = armed_load(a, off);
+    if (qc_slot_ready(v, b, want)) return true;
+    if (qc_cancelled(v, want, a.halt) || wall_clock64() - t0 > a.budget) return false;
+    if (a.spin == 0) {
+      __builtin_amdgcn_s_sleep(2);
+    } else if (a.spin >= 1000) {  // (experiments) (spin - 1000) x s_sleep(8) between polls
+      for (uint32_t j = 1000; j < a.spin; ++j) __builtin_amdgcn_s_sleep(8);
+    } else if (a.spin > 1) {
+      uint32_t x = lane;
+      for (uint32_t j = 0; j < a.spin; ++j) asm volatile("v_mad_u32_u24 %0, %0, %0, %0" : "+v"(x));
+    }
+  }
+}
+// A helper's wait: the relay word once its number is not `last`, or as it is
+// at the budget.  (Uncached memory: a relaxed system-scope load sees wave 0's
+// store with no cache maintenance; the host inputs read next were written
+// before the slot tags wave 0 saw, and host memory is not cached here.)
+__device__ __forceinline__ uint64_t armed_wait_relay(const ArmArgs& a, uint32_t last, uint64_t t0) {
+  for (;;) {
+    const uint64_t r = __hip_atomic_load(a.relay, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    if (qc_relay_number(r) != last || wall_clock64() - t0 > a.budget) return r;
+    __builtin_amdgcn_s_sleep(2);
+  }
+}
+// a helper's inputs, signature b of the mailbox arrays: one round trip
+__device__ __forceinline__ void armed_load_helper(const ArmArgs& a, uint32_t b, uint32_t lane, uint32_t e[8],
+                                                  uint32_t r[8], uint32_t s[8], uint32_t& key) {
+  qc_helper_decode(armed_load(a, qc_helper_off(b, lane)), e, r, s, key);
+}
+// slot wave b leaves (the helpers leave with wave 0: the relay first)
+__device__ __forceinline__ void armed_leave(const ArmArgs& a, uint32_t b, uint32_t lane, uint32_t want) {
+  if (lane != 0) return;
+  if (b == 0 && a.relay)
+    __hip_atomic_store(a.relay, qc_relay_pack(want, kQcRelayLeft), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  __hip_atomic_store(a.mail->expired(a.slot), want, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+// wave 0 announces a certificate wider than the slots to the helpers
+__device__ __forceinline__ void armed_announce(const ArmArgs& a, uint32_t b, uint32_t lane, uint32_t want, uint32_t n) {
+  if (b == 0 && a.relay && n > QcMail::kQcSlots && lane == 0)
+    __hip_atomic_store(a.relay, qc_relay_pack(want, n), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+// One lane's stores of slot b's verdict byte, after its GPU timestamps
+// (diagnostics: pbftv_qc_stamps*).  The armed path's layout is always cap =
+// kQcCap (no PCIe round trip for the header's cap between the verdict and its
+// store).  Coherent host memory is not cached on the GPU: the stores leave in
+// order; a system-scope release here would write back the L2 first.
+__device__ __forceinline__ void armed_store_verdict(const ArmArgs& a, uint32_t b, uint64_t seen_wall, uint64_t seen_clk,
+                                                    uint8_t res) {
+  constexpr uint32_t cap = QcMail::kQcCap;
+  uint8_t* const base = reinterpret_cast<uint8_t*>(a.mail);
+  if (a.stamps) {
+    volatile uint64_t* st = reinterpret_cast<volatile uint64_t*>(base + QcMail::stamps_off(cap)) + 4 * b;
+    st[0] = seen_wall;
+    st[1] = seen_clk;
+    st[2] = wall_clock64();
+    st[3] = clock64();
+  }
+  reinterpret_cast<volatile uint8_t*>(base)[QcMail::res_off(cap) + b] = res;
 }
 
 // Launched with kQcSlots waves (narrow) or kQcCap waves (wide: certificates
 // of up to 128 signatures, e.g. a 67-vote QC of an n = 100 committee).  Waves
 // past the slots are HELPERS: they never poll host memory; wave 0 relays each
 // request's number and n to them through a word of uncached device memory
-// (`relay`: {number, n}, n = ~0 when wave 0 leaves), and a helper whose index is below n
-// reads its signature from the mailbox arrays (one PCIe round trip; the host
-// writes them before the slot tags) and writes its verdict byte.
+// (`relay`, qc_mail.h), and a helper whose index is below n reads its
+// signature from the mailbox arrays and writes its verdict byte.
 template <int WG, int WQ>
 __global__ void __launch_bounds__(256) k_ecdsa_wave_armed(ArmArgs a) {
   // four waves per workgroup: one CU takes a workgroup's waves on its four
   // SIMDs, so no two armed waves of a workgroup share a SIMD's issue slots
   const uint32_t b = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
-  QcMail* const mail = a.mail;
-  uint8_t* const base = reinterpret_cast<uint8_t*>(mail);
+  uint8_t* const base = reinterpret_cast<uint8_t*>(a.mail);
   uint32_t want = a.want;
   const uint64_t t0 = wall_clock64();
   // live: this wave is resident (a rotation retires the old kernel after all are)
   if (lane == 0) reinterpret_cast<volatile uint32_t*>(base + QcMail::live_off(a.slot))[b] = want;
-  // key data for keys < 128, two per lane (lane l: keys l and l + 64)
-  const uint32_t nkeys = a.nkeys;
-  const uint4* qt_lo = lane < nkeys ? reinterpret_cast<const uint4* const*>(a.qtabs)[lane] : nullptr;
-  const uint4* qt_hi = lane + 64 < nkeys ? reinterpret_cast<const uint4* const*>(a.qtabs)[lane + 64] : nullptr;
-  const uint32_t kv_lo = lane < nkeys ? a.key_valid[lane] : 0u, kv_hi = lane + 64 < nkeys ? a.key_valid[lane + 64] : 0u;
+  ArmedKeys keys;
+  keys.load(a, lane);
   const uint4* gtab = reinterpret_cast<const uint4*>(a.gtab);
-  const uint4* const* qtabs = reinterpret_cast<const uint4* const*>(a.qtabs);
-  uint64_t* const relay = a.relay;
+  uint32_t e[8], r[8], s[8], k;
+  bool key_ok;
+  const uint4* qtab;
   if (b >= QcMail::kQcSlots) {
     // ---- helper wave ----
-    uint32_t last = 0;  // the relay starts at {0, 0}; request numbers are never 0
-    for (;;) {
-      uint64_t r = 0;
-      for (;;) {
-        // (uncached memory: a relaxed system-scope load sees wave 0's store
-        // with no cache maintenance; the host inputs read next were written
-        // before the slot tags wave 0 saw, and host memory is not cached here)
-        r = __hip_atomic_load(relay, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        if ((uint32_t)r != last || wall_clock64() - t0 > a.budget) break;
-        __builtin_amdgcn_s_sleep(2);
-      }
-      const uint32_t seq = (uint32_t)r, n = (uint32_t)(r >> 32);
-      if (seq == last || n == 0xFFFFFFFFu) return;  // budget, or wave 0 left
-      last = seq;
-      if (b >= n) continue;
+    for (uint32_t last = 0;;) {  // (its last relayed request)
+      const uint64_t rv = armed_wait_relay(a, last, t0);
+      if (qc_relay_number(rv) == last || qc_relay_n(rv) == kQcRelayLeft) return;  // budget, or wave 0 left
+      last = qc_relay_number(rv);
+      if (b >= qc_relay_n(rv)) continue;
       const uint64_t seen_wall = wall_clock64(), seen_clk = clock64();
       __builtin_amdgcn_s_setprio(3);
-      constexpr uint32_t cap = QcMail::kQcCap;  // the armed path's layout (the host relays it out only after a disarm)
-      // lanes 0-7 the hash, 8-23 r || s, 24 the key index: one round trip
-      const uint32_t* src = lane < 8    ? reinterpret_cast<const uint32_t*>(base + QcMail::hashes_off(cap) + 32 * b) + lane
-                            : lane < 24 ? reinterpret_cast<const uint32_t*>(base + QcMail::sigs_off(cap) + 64 * b) + (lane - 8)
-                                        : reinterpret_cast<const uint32_t*>(base + QcMail::keys_off(cap) + 4 * b);
-      const uint32_t v = __hip_atomic_load(src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      uint32_t e[8], rr[8], ss[8];
-      PBFTV_UNROLL for (int t = 0; t < 8; ++t) {
-        e[7 - t] = bswap32(__builtin_amdgcn_readlane(v, t));
-        rr[7 - t] = bswap32(__builtin_amdgcn_readlane(v, 8 + t));
-        ss[7 - t] = bswap32(__builtin_amdgcn_readlane(v, 16 + t));
-      }
-      bool key_ok;
-      const uint4* qtab;
-      armed_key(__builtin_amdgcn_readlane(v, 24), nkeys, qt_lo, qt_hi, kv_lo, kv_hi, a.key_valid, qtabs, key_ok, qtab);
-      const bool ok = wave_verify_words<WG, WQ>(e, rr, ss, key_ok, gtab, qtab);
-      if (lane == 0) {
-        if (a.stamps) {
-          volatile uint64_t* st = reinterpret_cast<volatile uint64_t*>(base + QcMail::stamps_off(cap)) + 4 * b;
-          st[0] = seen_wall;  // diagnostics (pbftv_qc_stamps_all), before the verdict
-          st[1] = seen_clk;
-          st[2] = wall_clock64();
-          st[3] = clock64();
-        }
-        reinterpret_cast<volatile uint8_t*>(base)[QcMail::res_off(cap) + b] = ok ? 1 : 0;
-      }
+      armed_load_helper(a, b, lane, e, r, s, k);
+      keys.lookup(a, k, key_ok, qtab);
+      const bool ok = wave_verify_words<WG, WQ>(e, r, s, key_ok, gtab, qtab);
+      if (lane == 0) armed_store_verdict(a, b, seen_wall, seen_clk, ok ? 1 : 0);
       __builtin_amdgcn_s_setprio(0);
     }
   }
   // ---- slot wave ----
-  const uint32_t* slot = reinterpret_cast<const uint32_t*>(base + QcMail::slot_off(b));
-  const uint32_t* word = lane < 48 ? slot + lane : reinterpret_cast<const uint32_t*>(base) + (lane - 48);
+  const size_t off = qc_poll_off(b, lane);
   for (;; ++want) {
-    uint32_t v = 0;
-    bool serve = false;
-    for (;;) {
-      v = __hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      // line 0 carries n; a slot past n needs only that line (the host writes
-      // no inputs there), a slot below n all three
-      if (__builtin_amdgcn_readlane(v, 0) == want && __builtin_amdgcn_readlane(v, 15) == want &&
-          (b >= __builtin_amdgcn_readlane(v, 1) ||
-           (__builtin_amdgcn_readlane(v, 16) == want && __builtin_amdgcn_readlane(v, 31) == want &&
-            __builtin_amdgcn_readlane(v, 32) == want && __builtin_amdgcn_readlane(v, 47) == want))) {
-        serve = true;
-        break;
-      }
-      if (__builtin_amdgcn_readlane(v, 48 + 2) == want || __builtin_amdgcn_readlane(v, 48 + 5) != a.halt ||
-          wall_clock64() - t0 > a.budget)
-        break;  // header stop / halt, or the budget
-      if (a.spin == 0) {
-        __builtin_amdgcn_s_sleep(2);
-      } else if (a.spin >= 1000) {  // (experiments) (spin - 1000) x s_sleep(8) between polls
-        for (uint32_t j = 1000; j < a.spin; ++j) __builtin_amdgcn_s_sleep(8);
-      } else if (a.spin > 1) {
-        uint32_t x = lane;
-        for (uint32_t j = 0; j < a.spin; ++j) asm volatile("v_mad_u32_u24 %0, %0, %0, %0" : "+v"(x));
-      }
-    }
-    if (!serve) {
-      if (b == 0 && relay && lane == 0)  // the helpers leave with wave 0
-        __hip_atomic_store(relay, ((uint64_t)0xFFFFFFFFu << 32) | want, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      if (lane == 0) __hip_atomic_store(mail->expired(a.slot), want, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    WaveSnap v;
+    if (!armed_wait_slot(a, b, lane, off, want, t0, v)) {
+      armed_leave(a, b, lane, want);
       return;
     }
     const uint64_t seen_wall = wall_clock64(), seen_clk = clock64();
-    const uint32_t n = __builtin_amdgcn_readlane(v, 1);
-    if (b == 0 && relay && n > QcMail::kQcSlots && lane == 0)
-      __hip_atomic_store(relay, ((uint64_t)n << 32) | want, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    const uint32_t n = qc_slot_n(v);
+    armed_announce(a, b, lane, want, n);
     if (b >= n) continue;
     // a certificate's waves go ahead of whatever else shares their SIMDs (the
     // waves of a large batch: issue priority only, nothing is preempted)
     __builtin_amdgcn_s_setprio(3);
-    uint32_t e[8], r[8], s[8];
-    const uint32_t k = __builtin_amdgcn_readlane(v, 2);
-    PBFTV_UNROLL for (int t = 0; t < 8; ++t) {  // slot line j, dword 4 + t = LE dword t of the hash / r / s
-      e[7 - t] = bswap32(__builtin_amdgcn_readlane(v, 4 + t));
-      r[7 - t] = bswap32(__builtin_amdgcn_readlane(v, 20 + t));
-      s[7 - t] = bswap32(__builtin_amdgcn_readlane(v, 36 + t));
-    }
-    bool key_ok;
-    const uint4* qtab;
-    armed_key(k, nkeys, qt_lo, qt_hi, kv_lo, kv_hi, a.key_valid, qtabs, key_ok, qtab);
+    qc_slot_decode(v, e, r, s, k);
+    keys.lookup(a, k, key_ok, qtab);
     const bool ok = wave_verify_words<WG, WQ>(e, r, s, key_ok, gtab, qtab);
-    if (lane == 0) {
-      // the armed path's layout is always cap = kQcCap (no PCIe round trip for
-      // the header's cap between the verdict and its store)
-      constexpr uint32_t cap = QcMail::kQcCap;
-      if (a.stamps) {
-        volatile uint64_t* st = reinterpret_cast<volatile uint64_t*>(base + QcMail::stamps_off(cap)) + 4 * b;
-        st[0] = seen_wall;  // diagnostics (pbftv_qc_stamps), before the verdict
-        st[1] = seen_clk;
-        st[2] = wall_clock64();
-        st[3] = clock64();
-      }
-      // (coherent host memory is not cached on the GPU: the stores leave in
-      // order; a system-scope release here would write back the L2 first)
-      reinterpret_cast<volatile uint8_t*>(base)[QcMail::res_off(cap) + b] = ok ? 1 : 0;
-    }
+    if (lane == 0) armed_store_verdict(a, b, seen_wall, seen_clk, ok ? 1 : 0);
     __builtin_amdgcn_s_setprio(0);
   }
 }
@@ -1777,114 +1777,55 @@ __global__ void __launch_bounds__(64 * kRowWaves) k_ecdsa_rows_armed(ArmArgs a) 
   __shared__ RowsShared sh;
   __shared__ uint32_t cmd;  // 0: leave, 1: serve the slot, 2: request without this slot
   const uint32_t b = blockIdx.x, lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
-  QcMail* const mail = a.mail;
-  uint8_t* const base = reinterpret_cast<uint8_t*>(mail);
+  uint8_t* const base = reinterpret_cast<uint8_t*>(a.mail);
   uint32_t want = a.want;
   const uint64_t t0 = wall_clock64();
   if (wv == 0 && lane == 0) reinterpret_cast<volatile uint32_t*>(base + QcMail::live_off(a.slot))[b] = want;
-  const uint32_t nkeys = a.nkeys;
-  const uint4* qt_lo = nullptr;
-  const uint4* qt_hi = nullptr;
-  uint32_t kv_lo = 0, kv_hi = 0;
-  if (wv == 0) {  // key data for keys < 128, two per lane
-    qt_lo = lane < nkeys ? reinterpret_cast<const uint4* const*>(a.qtabs)[lane] : nullptr;
-    qt_hi = lane + 64 < nkeys ? reinterpret_cast<const uint4* const*>(a.qtabs)[lane + 64] : nullptr;
-    kv_lo = lane < nkeys ? a.key_valid[lane] : 0u;
-    kv_hi = lane + 64 < nkeys ? a.key_valid[lane + 64] : 0u;
-  }
+  ArmedKeys keys;
+  if (wv == 0) keys.load(a, lane);
   const uint4* gtab = reinterpret_cast<const uint4*>(a.gtab);
-  const uint4* const* qtabs = reinterpret_cast<const uint4* const*>(a.qtabs);
   const bool helper = b >= QcMail::kQcSlots;  // (wide kernel only)
-  uint64_t* const relay = a.relay;
-  uint32_t last = 0;  // a helper's last relayed request (the relay starts at {0, 0}; numbers are never 0)
-  const uint32_t* slot = reinterpret_cast<const uint32_t*>(base + QcMail::slot_off(helper ? 0 : b));
-  const uint32_t* word = lane < 48 ? slot + lane : reinterpret_cast<const uint32_t*>(base) + (lane - 48);
+  uint32_t last = 0;  // a helper's last relayed request
+  const size_t off = qc_poll_off(helper ? 0 : b, lane);
   // this CU's word in the yield flags (and its instruction-cache partner's: cuyield 2)
   uint32_t* const cuf = a.cuflag ? a.cuflag + cu_flag_index() : nullptr;
   uint32_t* const cuf2 = cuf && a.cuyield == 2 ? a.cuflag + (cu_flag_index() ^ 1u) : nullptr;
   for (;; ++want) {
-    uint32_t e[8] = {}, r[8] = {}, s[8] = {};
+    uint32_t e[8] = {}, r[8] = {}, s[8] = {}, k = 0;
     bool key_ok = false;
     const uint4* qtab = nullptr;
     uint64_t seen_wall = 0, seen_clk = 0;
     if (wv == 0 && helper) {
-      // ---- a helper workgroup's wave 0: wave 0 of workgroup 0 relays each
-      // request's number and n through uncached device memory (see
-      // k_ecdsa_wave_armed); a slot below n reads its signature from the
-      // mailbox arrays in one round trip
-      uint64_t rv = 0;
-      for (;;) {
-        rv = __hip_atomic_load(relay, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        if ((uint32_t)rv != last || wall_clock64() - t0 > a.budget) break;
-        __builtin_amdgcn_s_sleep(2);
-      }
-      const uint32_t seq = (uint32_t)rv, n = (uint32_t)(rv >> 32);
+      const uint64_t rv = armed_wait_relay(a, last, t0);
       uint32_t c = 0;
-      if (seq != last && n != 0xFFFFFFFFu) {
-        last = seq;
-        c = b < n ? 1u : 2u;
+      if (qc_relay_number(rv) != last && qc_relay_n(rv) != kQcRelayLeft) {
+        last = qc_relay_number(rv);
+        c = b < qc_relay_n(rv) ? 1u : 2u;
         if (c == 1u) {
           seen_wall = wall_clock64();
           seen_clk = clock64();
-          constexpr uint32_t cap = QcMail::kQcCap;
-          const uint32_t* src = lane < 8    ? reinterpret_cast<const uint32_t*>(base + QcMail::hashes_off(cap) + 32 * b) + lane
-                                : lane < 24 ? reinterpret_cast<const uint32_t*>(base + QcMail::sigs_off(cap) + 64 * b) + (lane - 8)
-                                            : reinterpret_cast<const uint32_t*>(base + QcMail::keys_off(cap) + 4 * b);
-          const uint32_t v = __hip_atomic_load(src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-          PBFTV_UNROLL for (int t = 0; t < 8; ++t) {
-            e[7 - t] = bswap32(__builtin_amdgcn_readlane(v, t));
-            r[7 - t] = bswap32(__builtin_amdgcn_readlane(v, 8 + t));
-            s[7 - t] = bswap32(__builtin_amdgcn_readlane(v, 16 + t));
-          }
-          armed_key(__builtin_amdgcn_readlane(v, 24), nkeys, qt_lo, qt_hi, kv_lo, kv_hi, a.key_valid, qtabs, key_ok, qtab);
+          armed_load_helper(a, b, lane, e, r, s, k);
+          keys.lookup(a, k, key_ok, qtab);
         }
       }
       if (c == 1u) raise_cu_flags(cuf, cuf2);
       if (lane == 0) cmd = c;
     } else if (wv == 0) {
-      uint32_t v = 0;
-      bool serve = false;
-      for (;;) {
-        v = __hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        if (__builtin_amdgcn_readlane(v, 0) == want && __builtin_amdgcn_readlane(v, 15) == want &&
-            (b >= __builtin_amdgcn_readlane(v, 1) ||
-             (__builtin_amdgcn_readlane(v, 16) == want && __builtin_amdgcn_readlane(v, 31) == want &&
-              __builtin_amdgcn_readlane(v, 32) == want && __builtin_amdgcn_readlane(v, 47) == want))) {
-          serve = true;
-          break;
-        }
-        if (__builtin_amdgcn_readlane(v, 48 + 2) == want || __builtin_amdgcn_readlane(v, 48 + 5) != a.halt ||
-            wall_clock64() - t0 > a.budget)
-          break;  // header stop / halt, or the budget
-        if (a.spin == 0) {
-          __builtin_amdgcn_s_sleep(2);
-        } else if (a.spin >= 1000) {  // (experiments) (spin - 1000) x s_sleep(8) between polls
-          for (uint32_t j = 1000; j < a.spin; ++j) __builtin_amdgcn_s_sleep(8);
-        } else if (a.spin > 1) {
-          uint32_t x = lane;
-          for (uint32_t j = 0; j < a.spin; ++j) asm volatile("v_mad_u32_u24 %0, %0, %0, %0" : "+v"(x));
-        }
-      }
+      // (the helper's steps again, not joined with them: joined, the compiler
+      // copies e, r, s once more on the way to the barrier)
+      WaveSnap v;
       uint32_t c = 0;
-      if (!serve) {
-        if (b == 0 && relay && lane == 0)  // the helpers leave with workgroup 0
-          __hip_atomic_store(relay, ((uint64_t)0xFFFFFFFFu << 32) | want, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        if (lane == 0) __hip_atomic_store(mail->expired(a.slot), want, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+      if (!armed_wait_slot(a, b, lane, off, want, t0, v)) {
+        armed_leave(a, b, lane, want);
       } else {
         seen_wall = wall_clock64();
         seen_clk = clock64();
-        const uint32_t n = __builtin_amdgcn_readlane(v, 1);
-        if (b == 0 && relay && n > QcMail::kQcSlots && lane == 0)
-          __hip_atomic_store(relay, ((uint64_t)n << 32) | want, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        const uint32_t n = qc_slot_n(v);
+        armed_announce(a, b, lane, want, n);
         c = b < n ? 1u : 2u;
         if (c == 1u) {
-          const uint32_t k = __builtin_amdgcn_readlane(v, 2);
-          PBFTV_UNROLL for (int t = 0; t < 8; ++t) {  // slot line j, dword 4 + t = LE dword t of the hash / r / s
-            e[7 - t] = bswap32(__builtin_amdgcn_readlane(v, 4 + t));
-            r[7 - t] = bswap32(__builtin_amdgcn_readlane(v, 20 + t));
-            s[7 - t] = bswap32(__builtin_amdgcn_readlane(v, 36 + t));
-          }
-          armed_key(k, nkeys, qt_lo, qt_hi, kv_lo, kv_hi, a.key_valid, qtabs, key_ok, qtab);
+          qc_slot_decode(v, e, r, s, k);
+          keys.lookup(a, k, key_ok, qtab);
         }
       }
       if (c == 1u) raise_cu_flags(cuf, cuf2);
@@ -1901,17 +1842,7 @@ __global__ void __launch_bounds__(64 * kRowWaves) k_ecdsa_rows_armed(ArmArgs a) 
       __hip_atomic_fetch_sub(cuf, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       if (cuf2) __hip_atomic_fetch_sub(cuf2, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-    if (wv == 0 && lane == 0) {
-      constexpr uint32_t cap = QcMail::kQcCap;
-      if (a.stamps) {
-        volatile uint64_t* st = reinterpret_cast<volatile uint64_t*>(base + QcMail::stamps_off(cap)) + 4 * b;
-        st[0] = seen_wall;  // diagnostics (pbftv_qc_stamps), before the verdict
-        st[1] = seen_clk;
-        st[2] = wall_clock64();
-        st[3] = clock64();
-      }
-      reinterpret_cast<volatile uint8_t*>(base)[QcMail::res_off(cap) + b] = (uint8_t)ok;
-    }
+    if (wv == 0 && lane == 0) armed_store_verdict(a, b, seen_wall, seen_clk, (uint8_t)ok);
     __builtin_amdgcn_s_setprio(0);
   }
 }

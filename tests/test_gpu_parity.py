@@ -721,6 +721,83 @@ def test_split_wide_certificates(oracle_lib, monkeypatch):
             assert c1["reruns"] == c0["reruns"] and not c1["armed_wide"], (n, c0, c1)
 
 
+def test_armed_key_lookup_seams(oracle_lib, monkeypatch):
+    """Key indices at the seams of the armed kernels' key lookup (ArmedKeys in
+    verify_kernels.h: keys < 64 from the low half of a per-lane prefetch,
+    64..127 from its high half, >= 128 from memory, >= nkeys no key) through
+    an armed server: 130 registered keys, those at 1, 65 and 129 off the curve;
+    valid signatures and corrupted twins under 0, 1, 63, 64, 65, 127, 128 and
+    129, and rows naming keys 130 and 0xFFFFFFFF.  Served as certificates of
+    4..8 (each row at slot 0 and at a later slot) and of 67 (each row at
+    positions 0, 7, 8 and 66: the first and last slot, the first and last
+    helper); every call armed and of the right shape (pbftv_qc_counters).
+    Geometry (16, 8): 264-KiB key tables, and no row schedule, so
+    k_ecdsa_wave_armed serves both shapes.  k_ecdsa_rows_armed cannot be
+    given 130 keys in a test's time (its smallest key table is hundreds of MB
+    per key); it is covered because it looks keys up with the same struct.
+    In-range rows against the oracle; an out-of-range row expects the literal
+    0 (test_ecdsa_no_keys_and_out_of_range pins that for the launched path)."""
+    import time
+    from simple_pbft_amd import Verifier
+    seams, bad_keys, nk = (0, 1, 63, 64, 65, 127, 128, 129), (1, 65, 129), 130
+    monkeypatch.setenv("PBFTV_GBITS", "16")
+    monkeypatch.setenv("PBFTV_QBITS", "8")
+    monkeypatch.setenv("PBFTV_QC_ARM", "1")
+    monkeypatch.setenv("PBFTV_QC_ARM_MS", "30000")  # (no keeper rotation within the test)
+    for k in ("PBFTV_WAVE_MAX", "PBFTV_QC_ROWS", "PBFTV_QC_BUSY_ONE_WAVE", "PBFTV_QC_WIDE", "PBFTV_QC_SLOTS"):
+        monkeypatch.delenv(k, raising=False)
+    keys, ph, ps, _ = oracle_sign_pool(oracle_lib, n_keys=nk, per_key=1, seed=0x5EA5)  # signature k under key k
+    for k in bad_keys:
+        keys[k, 63] ^= 1
+        assert not oracle_lib.oracle_p256_key_valid(keys[k].ctypes.data)
+    # the seam rows (valid, twin per key; then the two out-of-range rows), then fillers under the other keys
+    rows = [(k, k, twin) for k in seams for twin in (False, True)] + [(0, nk, False), (0, 0xFFFFFFFF, False)]
+    n_seam = len(rows)
+    rows += [(k, k, k % 5 == 0) for k in range(nk) if k not in seams]
+    H = np.stack([ph[src] for src, _, _ in rows])
+    S = np.stack([ps[src] for src, _, _ in rows])
+    K = np.array([k for _, k, _ in rows], np.uint32)
+    twin = np.array([t for _, _, t in rows])
+    S[twin, 40] ^= 0x04
+    in_range = K < nk
+    want = np.zeros(len(K), bool)
+    Hi, Si, Ki = (np.ascontiguousarray(a[in_range]) for a in (H, S, K))
+    bm = np.zeros((len(Ki) + 7) // 8, np.uint8)
+    oracle_lib.oracle_ecdsa_p256_verify_batch(Hi.ctypes.data, Si.ctypes.data, Ki.ctypes.data, len(Ki), keys.ctypes.data,
+                                              nk, bm.ctypes.data, 8)
+    want[in_range] = np.unpackbits(bm, bitorder="little")[:len(Ki)].astype(bool)
+    assert (want == (in_range & ~twin & ~np.isin(K, bad_keys))).all()
+    fill = np.arange(n_seam, len(K))
+
+    def call(v, idx, wide):
+        c0 = v.qc_counters(0)
+        got = v.verify_batch(H[idx], S[idx], K[idx])
+        c1 = v.qc_counters(0)
+        assert (got == want[idx]).all(), (K[idx].tolist(), got.tolist())
+        return tuple(c1[k] - c0[k] for k in ("calls", "armed", "launches")) == (1, 1, 0) and c1["armed_wide"] == wide
+
+    def wait_armed(v, idx, wide):
+        t0 = time.monotonic()
+        while not call(v, idx, wide):  # (the keeper arms after the first call; a wide kernel needs all workgroups resident)
+            assert time.monotonic() - t0 < 5.0, v.qc_counters(0)
+            time.sleep(0.01)
+
+    with Verifier(device_mask=1) as v:
+        valid = v.register_keys(keys)
+        assert np.nonzero(~np.asarray(valid, bool))[0].tolist() == list(bad_keys)
+        assert v.table_config()[:2] == (16, 8)
+        monkeypatch.setenv("PBFTV_QC_WIDE", "0")
+        wait_armed(v, fill[:8], wide=False)  # (a certificate of 8: the narrow server arms all its slots)
+        for j in range(n_seam):  # row j at slot 0; at a later slot in the certificate before
+            assert call(v, (j + np.arange(4 + j % 5)) % n_seam, wide=False), (j, v.qc_counters(0))
+        monkeypatch.delenv("PBFTV_QC_WIDE")
+        wait_armed(v, fill[:67], wide=True)  # (the first wide call is launched, the next arming is wide)
+        for j in range(n_seam):
+            idx = fill[(j + np.arange(67)) % len(fill)]
+            idx[[0, 7, 8, 66]] = (j + np.arange(4)) % n_seam
+            assert call(v, idx, wide=True), (j, v.qc_counters(0))
+
+
 def test_armed_kernel_does_not_hold_frees_or_other_contexts(oracle_lib, monkeypatch):
     """An armed kernel with a 5-s budget stays resident between calls.  A
     device free and a pinned-host free neither wait for it nor stop it
