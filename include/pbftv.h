@@ -48,6 +48,7 @@ extern "C" {
 #define PBFTV_EDEVICE (-3)  /* HIP runtime / kernel error; see pbftv_last_error() */
 #define PBFTV_ENOMEM (-4)   /* device or pinned host allocation failed */
 #define PBFTV_ENOKEYS (-5)  /* verify called before pbftv_register_keys */
+#define PBFTV_ENOSIGNKEYS (-6) /* sign called before pbftv_register_signing_keys */
 
 typedef struct pbftv_ctx pbftv_ctx;
 
@@ -182,7 +183,13 @@ int pbftv_set_latency_path_max(pbftv_ctx* ctx, uint64_t n);
  * normalised to r||s: pbftv_ecdsa_der_to_rs_batch_dev and every *_der verify
  * and flush), timed and reset with the others.  pbftv_kernel_time_ms accepts
  * the ids 0..5 it always did (any other is PBFTV_EINVAL, as callers may rely
- * on); id 6 is read through pbftv_der_kernel_time_ms, same outputs. */
+ * on); id 6 is read through pbftv_der_kernel_time_ms, same outputs.
+ * Timing id 7, PBFTV_K_ECDSA_SIGN, is the signer's kernels (the sign batches
+ * and pbftv_sign_replies below), timed and reset with the others and read
+ * through pbftv_sign_kernel_time_ms: stage 0 = all of them summed, 1 = nonce
+ * (RFC 6979 DRBG, k^-1), 2 = comb (k*G, r), 3 = tail (s, the rows and ok
+ * bits), 4 = the DER writer; out_launches counts the launches of the stage
+ * asked for (a sign batch is one launch of each of 1..3). */
 #define PBFTV_K_ECDSA_SCALARS 0
 #define PBFTV_K_ECDSA_COMB 1
 #define PBFTV_K_SHA256 2
@@ -190,9 +197,11 @@ int pbftv_set_latency_path_max(pbftv_ctx* ctx, uint64_t n);
 #define PBFTV_K_GOJSON 4
 #define PBFTV_K_ECDSA_VARBASE 5
 #define PBFTV_K_ECDSA_DER 6
+#define PBFTV_K_ECDSA_SIGN 7
 int pbftv_set_kernel_timing(pbftv_ctx* ctx, int enable);
 int pbftv_kernel_time_ms(pbftv_ctx* ctx, int dev, int kernel, double* out_ms, uint64_t* out_launches);
 int pbftv_der_kernel_time_ms(pbftv_ctx* ctx, int dev, double* out_ms, uint64_t* out_launches);
+int pbftv_sign_kernel_time_ms(pbftv_ctx* ctx, int dev, int stage, double* out_ms, uint64_t* out_launches);
 int pbftv_reset_kernel_times(pbftv_ctx* ctx);
 /* Diagnostics of the last latency-path call (n <= 2048) on device dev:
  * out[0] = host ns from entry to the request being handed over (bell rung or
@@ -679,6 +688,67 @@ int pbftv_flush_replies_wirekey_der(pbftv_ctx* ctx, uint64_t n, const int64_t* v
                                     const uint64_t* result_off, const uint32_t* result_len, const uint8_t* der,
                                     const uint64_t* der_off, const uint32_t* der_len, const uint8_t* keys,
                                     int key_format, uint8_t* out_digests, uint8_t* out_sig_bitmap);
+
+/* ---- Signing: deterministic ECDSA-P256 in batches ----
+ * What a replica sends it signs here: Go's crypto/ecdsa.Sign over a 32-byte
+ * digest with the nonce of RFC 6979 section 3.2 (HMAC-SHA256, no additional
+ * data), so a (digest, key) pair always gives the same signature.  No low-S
+ * normalisation, as in Go; every verify of this library accepts the result.
+ *
+ * pbftv_register_signing_keys takes k private keys, 32 big-endian bytes each,
+ * and replaces any previous set; out_valid[j] (may be NULL) is 0 for d = 0 or
+ * d >= n, and such a key signs nothing.  It waits for the context's in-flight
+ * work as pbftv_register_keys does.  The keys live in device memory only: the
+ * device copy is overwritten with zeros before it is freed or replaced and at
+ * pbftv_close, the host staging copy before the call returns, and no call
+ * copies a private key back.  The set is independent of the verify keys: no
+ * call in this section needs, reads or disturbs pbftv_register_keys' set.
+ * Nonces never steer a branch on the device, but the G comb entry a lane
+ * loads is addressed by its nonce's digits: the GPU and whoever shares it are
+ * trusted.
+ *
+ * The batch calls sign hashes[i] (32 B) under key skey_idx[i] into
+ * out_sig_rs[i] (64 B, r||s big-endian, what the verifies take) and bit i of
+ * out_ok_bitmap (LSB-first, ceil(n/8) bytes, padding bits zero; may be NULL).
+ * An skey_idx out of range or naming an invalid key is never an error: that
+ * row is 64 zero bytes with a 0 bit.  n = 0 returns PBFTV_OK and writes
+ * nothing; n >= 2^32 is PBFTV_EINVAL; before any registration the calls
+ * return PBFTV_ENOSIGNKEYS.  The host form shards contiguously over the
+ * devices with plain copies.  The _dev form takes device pointers (hashes and
+ * signatures 16-B aligned), enqueues on `stream` (NULL: the context's) without
+ * synchronising, and is counted by the context's in-flight bookkeeping like
+ * any *_dev verify, so a verify enqueued behind it on the same stream reads
+ * the finished signatures with no host synchronisation in between.
+ *
+ * The _der forms write ASN.1 DER instead, what crypto/ecdsa.SignASN1 emits:
+ * signature i in the 72-byte slot out_der + 72 i (every byte of the slot is
+ * written; the _dev form wants the slots 16-B aligned), its length in
+ * out_der_len[i]; a length of 0 means not signed.
+ *
+ * pbftv_sign_replies takes the reply columns of pbftv_digest_reply_batch and
+ * does Go-JSON, SHA-256 and the signature in one round trip per device, the
+ * digests staying in device memory in between; out_digests may be NULL.  Votes
+ * have no call of their own: two per sequence compose from
+ * pbftv_digest_vote_batch followed by pbftv_ecdsa_p256_sign_batch. */
+int pbftv_register_signing_keys(pbftv_ctx* ctx, const uint8_t* priv, uint32_t k, uint8_t* out_valid);
+int pbftv_ecdsa_p256_sign_batch(pbftv_ctx* ctx, const uint8_t* hashes, const uint32_t* skey_idx, uint64_t n,
+                                uint8_t* out_sig_rs, uint8_t* out_ok_bitmap);
+int pbftv_ecdsa_p256_sign_batch_dev(pbftv_ctx* ctx, int dev, const uint8_t* d_hashes, const uint32_t* d_skey_idx,
+                                    uint64_t n, uint8_t* d_out_sig_rs, uint8_t* d_out_ok_bitmap, void* stream);
+int pbftv_ecdsa_p256_sign_der_batch(pbftv_ctx* ctx, const uint8_t* hashes, const uint32_t* skey_idx, uint64_t n,
+                                    uint8_t* out_der, uint32_t* out_der_len);
+int pbftv_ecdsa_p256_sign_der_batch_dev(pbftv_ctx* ctx, int dev, const uint8_t* d_hashes, const uint32_t* d_skey_idx,
+                                        uint64_t n, uint8_t* d_out_der, uint32_t* d_out_der_len, void* stream);
+int pbftv_sign_replies(pbftv_ctx* ctx, uint64_t n, const int64_t* view_ids, const int64_t* timestamps,
+                       const uint8_t* client_ids, const uint64_t* client_id_off, const uint32_t* client_id_len,
+                       const uint8_t* node_ids, const uint64_t* node_id_off, const uint32_t* node_id_len,
+                       const uint8_t* results, const uint64_t* result_off, const uint32_t* result_len,
+                       const uint32_t* skey_idx, uint8_t* out_digests, uint8_t* out_sig_rs, uint8_t* out_ok_bitmap);
+int pbftv_sign_replies_der(pbftv_ctx* ctx, uint64_t n, const int64_t* view_ids, const int64_t* timestamps,
+                           const uint8_t* client_ids, const uint64_t* client_id_off, const uint32_t* client_id_len,
+                           const uint8_t* node_ids, const uint64_t* node_id_off, const uint32_t* node_id_len,
+                           const uint8_t* results, const uint64_t* result_off, const uint32_t* result_len,
+                           const uint32_t* skey_idx, uint8_t* out_digests, uint8_t* out_der, uint32_t* out_der_len);
 
 /* Quorum certificate: verify n signatures and count acceptances.
  * *out_accepted = popcount; *out_quorum = (*out_accepted >= quorum).  With

@@ -172,6 +172,50 @@ struct DerDwordReader {
   }
 };
 
+// ---- the writer: r||s -> DER, what go's crypto/ecdsa.SignASN1 emits ----
+// SEQUENCE { INTEGER r, INTEGER s }, each INTEGER minimal: leading zero bytes
+// dropped (one byte stays for the value 0), a 00 pad in front when the top bit
+// of the first byte is set.  Every length is short form (an INTEGER has at
+// most 33 content bytes, the SEQUENCE at most 70), so the encoding is 8 to 72
+// bytes.  get(i): byte i of the 64 big-endian bytes r||s; put(i, b): byte i of
+// the 72-byte slot, every index 0..71 written once in rising order (zeros past
+// the encoding), so a slot never keeps bytes of an earlier use.  Returns the
+// encoding's length.
+template <class Get, class Put>
+PBFTV_DER_HD uint32_t der_write_rs(Get get, Put put) {
+  uint32_t skip[2], pad[2], len[2];
+  for (int v = 0; v < 2; ++v) {
+    uint32_t z = 0;
+    bool lead = true;
+    for (uint32_t i = 0; i < 31; ++i) {  // (byte 31 always stays)
+      lead = lead && get(32 * v + i) == 0;
+      z += lead ? 1u : 0u;
+    }
+    skip[v] = z;
+    pad[v] = (get(32 * v + z) & 0x80u) ? 1u : 0u;
+    len[v] = pad[v] + 32 - z;
+  }
+  const uint32_t body = 4 + len[0] + len[1], total = 2 + body;
+  uint32_t o = 0;
+  put(o++, 0x30u);
+  put(o++, body);
+  for (int v = 0; v < 2; ++v) {
+    put(o++, 0x02u);
+    put(o++, len[v]);
+    if (pad[v]) put(o++, 0x00u);
+    for (uint32_t i = skip[v]; i < 32; ++i) put(o++, get(32 * v + i));
+  }
+  for (; o < kDerMaxBytes; ++o) put(o, 0x00u);
+  return total;
+}
+
+// through pointers (the host, the CPU harness; the device's slots are global
+// memory it addresses the same way)
+PBFTV_DER_HD uint32_t der_from_rs(const uint8_t rs[64], uint8_t out[72]) {
+  return der_write_rs([&](uint32_t i) -> uint32_t { return rs[i]; },
+                      [&](uint32_t i, uint32_t b) { out[i] = (uint8_t)b; });
+}
+
 // r||s words -> 64 bytes on any host
 inline void der_store_rs(const uint32_t rs[16], uint8_t* out_rs) {
   for (int k = 0; k < 16; ++k)

@@ -181,6 +181,38 @@ hipError_t launch_varbase(const void* rec, const void* aux, uint64_t n, const ui
 hipError_t launch_der_to_rs(const uint8_t* data, const uint64_t* offsets, const uint32_t* lengths, uint64_t n,
                             uint8_t* out_rs, uint8_t* parsed, hipStream_t st);
 
+// ---- ECDSA-P256 signing (p256_sign.hip, sign.h) ----
+// One batch is the three stages in order on one stream: nonce (RFC 6979 DRBG,
+// k^-1), comb (k*G over the width-16 G table, r), tail (s, the r||s rows, the
+// ok bitmap).  keys: 8 LE words per private key, key_valid: one word per key
+// (sign_key_words / sign_key_valid make them on the host); rec:
+// sign_record_bytes(n) of scratch that holds the nonces between the stages and
+// is cleared of them by the tail.  out_rs: 64 B per signature, 16-B aligned,
+// zeros where skey_idx is out of range or names an invalid key; okbits (may be
+// null): LSB-first, ceil(n/8) B, padding bits zero.  n < 2^32.
+struct SignArgs {
+  const uint8_t* hashes;
+  const uint32_t* skey_idx;
+  const uint32_t* keys;
+  const uint32_t* key_valid;
+  uint32_t nkeys;
+  uint64_t n;
+  const uint32_t* gtab;
+  void* rec;
+  uint8_t* out_rs;
+  uint8_t* okbits;
+};
+constexpr int kSignStageNonce = 0, kSignStageComb = 1, kSignStageTail = 2, kSignStages = 3;
+size_t sign_record_bytes(uint64_t n);
+bool sign_key_valid(const uint8_t be[32]);  // 0 < d < n
+void sign_key_words(const uint8_t be[32], uint32_t out[8]);
+hipError_t launch_sign_stage(int stage, const SignArgs& a, hipStream_t st);
+// r||s rows -> minimal DER (der.h's writer) in 72-byte slots (out_der 8-B
+// aligned, every byte of a slot written) and their lengths; 0 and a zero slot
+// where okbits (not null here) has a 0
+hipError_t launch_sign_der(const uint8_t* rs, const uint8_t* okbits, uint64_t n, uint8_t* out_der, uint32_t* out_len,
+                           hipStream_t st);
+
 // ---- SHA-256 (sha256_kernels.hip) ----
 // data must stay readable 4 bytes past every message end (device allocations are padded).
 // order: optional permutation (lane -> message), used for block-count bucketing.

@@ -359,6 +359,23 @@ struct Device {
     double acc_ms = 0;
     uint64_t launches = 0;
   } der;
+  // Signing (p256_sign.hip): the private keys (8 LE words each, then one
+  // validity word each; wiped with zeros before the buffer is freed, replaced
+  // or the context closes), the stage records, the r||s rows and ok bits the
+  // DER forms and pbftv_sign_replies sign into (one of each per device, every
+  // use ordered by the scratch event like Device::der.rs), and timing id
+  // PBFTV_K_ECDSA_SIGN per stage (nonce, comb, tail, DER writer).  After every
+  // other member, as Device::der: no call that existed before reads any of it.
+  struct Sign {
+    DevBuf keys;
+    uint32_t nkeys = 0;
+    bool have = false;
+    DevBuf rec, rs, okb, der, der_len;
+    static constexpr int kStages = 4;
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> pending[kStages];
+    double acc_ms[kStages] = {0, 0, 0, 0};
+    uint64_t launches[kStages] = {0, 0, 0, 0};
+  } sign;
 };
 
 // key-order scratch: a fresh allocation gets its header zeroed (the sort's
@@ -1239,6 +1256,16 @@ std::vector<uint64_t> twice(std::vector<uint64_t> s, uint64_t* total) {
   return s;
 }
 
+// The device's private keys overwritten with zeros (d.mu held, device current);
+// the memset has completed on return.
+hipError_t sign_wipe_keys(Device& d) {
+  d.sign.have = false;
+  d.sign.nkeys = 0;
+  if (!d.sign.keys.p) return hipSuccess;
+  HIP_TRY_E(hipMemsetAsync(d.sign.keys.p, 0, d.sign.keys.cap, d.stream));
+  return hipStreamSynchronize(d.stream);
+}
+
 bool keys_ready(pbftv_ctx* ctx) {
   for (auto& dp : ctx->devs)
     if (!dp->have_keys) return false;
@@ -1257,6 +1284,7 @@ const char* pbftv_strerror(int code) {
     case PBFTV_EDEVICE: return "HIP device error";
     case PBFTV_ENOMEM: return "out of memory";
     case PBFTV_ENOKEYS: return "no keys registered";
+    case PBFTV_ENOSIGNKEYS: return "no signing keys registered";
     default: return "unknown error";
   }
 }
@@ -1310,6 +1338,9 @@ void pbftv_close(pbftv_ctx* ctx) {
     // and their scratch: they finish before anything below is freed
     for (auto& kv : d->stream_scratch) (void)hipStreamSynchronize(kv.first);
     (void)collect_times(*d);
+    (void)sign_wipe_keys(*d);  // zeros over the private keys before their memory goes back
+    for (DevBuf* b : {&d->sign.keys, &d->sign.rec, &d->sign.rs, &d->sign.okb, &d->sign.der, &d->sign.der_len})
+      b->release();
     for (auto& b : d->qblocks) b->release();
     for (auto& b : d->tab_scratch) b.release();
     d->tab_keys.release();
@@ -1697,6 +1728,27 @@ int pbftv_der_kernel_time_ms(pbftv_ctx* ctx, int dev, double* out_ms, uint64_t* 
   return PBFTV_OK;
 }
 
+// timing id PBFTV_K_ECDSA_SIGN (the sign stages): slots of its own (Device::sign)
+static hipError_t sign_collect_times(Device& d);
+
+int pbftv_sign_kernel_time_ms(pbftv_ctx* ctx, int dev, int stage, double* out_ms, uint64_t* out_launches) {
+  Device* d = dev_of(ctx, dev);
+  if (!d || stage < 0 || stage > Device::Sign::kStages) return fail(PBFTV_EINVAL, "bad argument");
+  std::lock_guard<std::mutex> lk(d->mu);
+  HIP_TRY(hipSetDevice(d->id));
+  HIP_TRY(sign_collect_times(*d));
+  double ms = 0;
+  uint64_t launches = 0;
+  for (int k = 0; k < Device::Sign::kStages; ++k)
+    if (stage == 0 || stage == k + 1) {
+      ms += d->sign.acc_ms[k];
+      launches += d->sign.launches[k];
+    }
+  if (out_ms) *out_ms = ms;
+  if (out_launches) *out_launches = launches;
+  return PBFTV_OK;
+}
+
 int pbftv_reset_kernel_times(pbftv_ctx* ctx) {
   if (!ctx) return fail(PBFTV_EINVAL, "ctx is null");
   for (auto& dp : ctx->devs) {
@@ -1710,6 +1762,11 @@ int pbftv_reset_kernel_times(pbftv_ctx* ctx) {
     HIP_TRY(der_collect_times(*dp));
     dp->der.acc_ms = 0;
     dp->der.launches = 0;
+    HIP_TRY(sign_collect_times(*dp));
+    for (int k = 0; k < Device::Sign::kStages; ++k) {
+      dp->sign.acc_ms[k] = 0;
+      dp->sign.launches[k] = 0;
+    }
   }
   return PBFTV_OK;
 }
@@ -2867,6 +2924,226 @@ int pbftv_ecdsa_p256_verify_wirekey_der_batch(pbftv_ctx* ctx, const uint8_t* has
   return verify_der_host_sharded(ctx, hashes, der, der_off, der_len, nullptr, keys, key_format, n, out_bitmap);
 }
 
+// ---- signing: RFC 6979 ECDSA-P256 in batches (sign.h, p256_sign.hip) ----
+// one timed launch of a sign stage (as timed(): events around it, collected by
+// pbftv_sign_kernel_time_ms)
+static int sign_timed(Device& d, int slot, hipStream_t st, const std::function<hipError_t()>& launch) {
+  if (!d.timing || !*d.timing) {
+    HIP_TRY(launch());
+    return PBFTV_OK;
+  }
+  hipEvent_t a, b;
+  HIP_TRY(hipEventCreate(&a));
+  HIP_TRY(hipEventCreate(&b));
+  (void)hipEventRecord(a, st);
+  const hipError_t e = launch();
+  (void)hipEventRecord(b, st);
+  d.sign.pending[slot].push_back({a, b});
+  HIP_TRY(e);
+  return PBFTV_OK;
+}
+
+static hipError_t sign_collect_times(Device& d) {
+  for (int k = 0; k < Device::Sign::kStages; ++k) {
+    for (auto& pr : d.sign.pending[k]) {
+      HIP_TRY_E(hipEventSynchronize(pr.second));
+      float ms = 0;
+      HIP_TRY_E(hipEventElapsedTime(&ms, pr.first, pr.second));
+      d.sign.acc_ms[k] += ms;
+      d.sign.launches[k] += 1;
+      (void)hipEventDestroy(pr.first);
+      (void)hipEventDestroy(pr.second);
+    }
+    d.sign.pending[k].clear();
+  }
+  return hipSuccess;
+}
+
+int pbftv_register_signing_keys(pbftv_ctx* ctx, const uint8_t* priv, uint32_t k, uint8_t* out_valid) {
+  if (!ctx || (k && !priv)) return fail(PBFTV_EINVAL, "null argument");
+  // host staging: the keys' words, then their validity words; zeroed below
+  std::vector<uint32_t> stage((size_t)k * 9 + 1, 0);
+  for (uint32_t j = 0; j < k; ++j) {
+    const bool ok = pbftv::sign_key_valid(priv + 32 * (size_t)j);
+    if (ok) pbftv::sign_key_words(priv + 32 * (size_t)j, stage.data() + 8 * (size_t)j);
+    stage[8 * (size_t)k + j] = ok ? 1u : 0u;
+    if (out_valid) out_valid[j] = ok ? 1 : 0;
+  }
+  const size_t bytes = (size_t)k * 36;
+  int rc = PBFTV_OK;
+  for (auto& dp : ctx->devs) {  // (plain copies: in turn, no host threads)
+    Device& d = *dp;
+    std::lock_guard<std::mutex> lk(d.mu);
+    rc = [&]() -> int {
+      HIP_TRY(hipSetDevice(d.id));
+      HIP_TRY(ctx_quiesce(d));  // nothing of this context still reads the old keys
+      HIP_TRY(sign_wipe_keys(d));
+      if (bytes + 64 > d.sign.keys.cap) {  // (the old buffer is zeros by now)
+        d.sign.keys.release();
+        HIP_TRY(d.sign.keys.ensure(bytes + 64));
+        HIP_TRY(hipMemsetAsync(d.sign.keys.p, 0, d.sign.keys.cap, d.stream));
+      }
+      if (bytes) HIP_TRY(hipMemcpyAsync(d.sign.keys.p, stage.data(), bytes, hipMemcpyHostToDevice, d.stream));
+      HIP_TRY(hipStreamSynchronize(d.stream));
+      d.sign.nkeys = k;
+      d.sign.have = true;
+      return PBFTV_OK;
+    }();
+    if (rc != PBFTV_OK) break;
+  }
+  volatile uint32_t* wipe = stage.data();
+  for (size_t i = 0; i < stage.size(); ++i) wipe[i] = 0;
+  if (rc != PBFTV_OK) {
+    for (auto& dp : ctx->devs) {  // no device keeps a signing key set the others lack
+      std::lock_guard<std::mutex> lk(dp->mu);
+      if (hipSetDevice(dp->id) == hipSuccess) (void)sign_wipe_keys(*dp);
+      dp->sign.have = false;
+    }
+  }
+  return rc;
+}
+
+static bool sign_keys_ready(pbftv_ctx* ctx) {
+  for (auto& dp : ctx->devs)
+    if (!dp->sign.have) return false;
+  return true;
+}
+
+// One batch on stream st (d.mu held): the three stages against the width-16 G
+// table (vb_gtab: the verify under unregistered keys takes the same one; built
+// on first use, kept while the context lives).  The stage records are one
+// buffer per device, ordered across streams by the scratch event exactly as
+// Device::der.rs is, so the context's quiesce and the deferred frees count this
+// work like any other *_dev call.  Reads nothing of the verify key set.
+static int sign_on_device(Device& d, const uint8_t* d_hashes, const uint32_t* d_skey_idx, uint64_t n,
+                          uint8_t* d_out_rs, uint8_t* d_okbits, hipStream_t st) {
+  if (n == 0) return PBFTV_OK;
+  if (!d.sign.have) return fail(PBFTV_ENOSIGNKEYS, "pbftv_register_signing_keys has not been called");
+  if (!d.vb_gtab) {
+    auto t0 = std::chrono::steady_clock::now();
+    const int r = acquire_g_table(d, pbftv::kVarbaseGBits, &d.vb_gtab, t0);
+    if (r != PBFTV_OK) return r;
+    HIP_TRY(hipDeviceGetAttribute(&d.vb_cus, hipDeviceAttributeMultiprocessorCount, d.id));
+  }
+  HIP_TRY(d.sign.rec.ensure(pbftv::sign_record_bytes(n)));
+  note_busy(d, n, 30.0);
+  const uint32_t* keys = d.sign.keys.as<uint32_t>();
+  const pbftv::SignArgs a{d_hashes, d_skey_idx, keys, keys + 8 * (size_t)d.sign.nkeys, d.sign.nkeys, n,
+                          d.vb_gtab->as<uint32_t>(), d.sign.rec.p, d_out_rs, d_okbits};
+  HIP_TRY(scratch_acquire(d, st));
+  int rc = PBFTV_OK;
+  for (int stage = 0; stage < pbftv::kSignStages && rc == PBFTV_OK; ++stage)
+    rc = sign_timed(d, stage, st, [&] { return pbftv::launch_sign_stage(stage, a, st); });
+  HIP_TRY(scratch_release(d, st));
+  return rc;
+}
+
+// ... and with the signatures written as DER: the batch signs into the
+// device's r||s rows and ok bits, the writer turns them into slots and lengths
+static int sign_der_on_device(Device& d, const uint8_t* d_hashes, const uint32_t* d_skey_idx, uint64_t n,
+                              uint8_t* d_out_der, uint32_t* d_out_len, hipStream_t st) {
+  if (n == 0) return PBFTV_OK;
+  if (!d.sign.have) return fail(PBFTV_ENOSIGNKEYS, "pbftv_register_signing_keys has not been called");
+  HIP_TRY(d.sign.rs.ensure(64 * n));
+  HIP_TRY(d.sign.okb.ensure((n + 7) / 8 + 8));
+  HIP_TRY(scratch_acquire(d, st));  // (rs and okb: held until the writer has read them)
+  int rc = sign_on_device(d, d_hashes, d_skey_idx, n, d.sign.rs.as<uint8_t>(), d.sign.okb.as<uint8_t>(), st);
+  if (rc == PBFTV_OK)
+    rc = sign_timed(d, 3, st, [&] {
+      return pbftv::launch_sign_der(d.sign.rs.as<uint8_t>(), d.sign.okb.as<uint8_t>(), n, d_out_der, d_out_len, st);
+    });
+  HIP_TRY(scratch_release(d, st));
+  return rc;
+}
+
+static int sign_dev_args(pbftv_ctx* ctx, int dev, uint64_t n) {
+  if (!ctx || dev < 0 || dev >= (int)ctx->devs.size()) return fail(PBFTV_EINVAL, "bad context or device index");
+  if (n >> 32) return fail(PBFTV_EINVAL, "n must be below 2^32");
+  return PBFTV_OK;
+}
+
+int pbftv_ecdsa_p256_sign_batch_dev(pbftv_ctx* ctx, int dev, const uint8_t* d_hashes, const uint32_t* d_skey_idx,
+                                    uint64_t n, uint8_t* d_out_sig_rs, uint8_t* d_out_ok_bitmap, void* stream) {
+  if (const int rc = sign_dev_args(ctx, dev, n)) return rc;
+  if (n == 0) return PBFTV_OK;
+  if (!d_hashes || !d_skey_idx || !d_out_sig_rs) return fail(PBFTV_EINVAL, "null buffer");
+  if (((uintptr_t)d_hashes | (uintptr_t)d_out_sig_rs) & 15u)
+    return fail(PBFTV_EINVAL, "hashes/signatures must be 16-B aligned");
+  Device& d = *ctx->devs[dev];
+  std::lock_guard<std::mutex> lk(d.mu);
+  HIP_TRY(hipSetDevice(d.id));
+  return sign_on_device(d, d_hashes, d_skey_idx, n, d_out_sig_rs, d_out_ok_bitmap, pick_stream(d, stream));
+}
+
+int pbftv_ecdsa_p256_sign_der_batch_dev(pbftv_ctx* ctx, int dev, const uint8_t* d_hashes, const uint32_t* d_skey_idx,
+                                        uint64_t n, uint8_t* d_out_der, uint32_t* d_out_der_len, void* stream) {
+  if (const int rc = sign_dev_args(ctx, dev, n)) return rc;
+  if (n == 0) return PBFTV_OK;
+  if (!d_hashes || !d_skey_idx || !d_out_der || !d_out_der_len) return fail(PBFTV_EINVAL, "null buffer");
+  if (((uintptr_t)d_hashes | (uintptr_t)d_out_der) & 15u)
+    return fail(PBFTV_EINVAL, "hashes/DER slots must be 16-B aligned");
+  Device& d = *ctx->devs[dev];
+  std::lock_guard<std::mutex> lk(d.mu);
+  HIP_TRY(hipSetDevice(d.id));
+  return sign_der_on_device(d, d_hashes, d_skey_idx, n, d_out_der, d_out_der_len, pick_stream(d, stream));
+}
+
+// Host forms: contiguous shards over the context's devices; each copies its
+// hashes and key indices in, signs on its stream and copies its signatures
+// (r||s rows and ok bits, or DER slots and lengths) back -- simple copies.
+static int sign_host(pbftv_ctx* ctx, const uint8_t* hashes, const uint32_t* skey_idx, uint64_t n, uint8_t* out_rs,
+                     uint8_t* out_ok, uint8_t* out_der, uint32_t* out_der_len) {
+  if (!ctx) return fail(PBFTV_EINVAL, "ctx is null");
+  if (n >> 32) return fail(PBFTV_EINVAL, "n must be below 2^32");
+  if (n == 0) return PBFTV_OK;
+  if (!hashes || !skey_idx || !(out_rs || (out_der && out_der_len))) return fail(PBFTV_EINVAL, "null buffer");
+  if (!sign_keys_ready(ctx)) return fail(PBFTV_ENOSIGNKEYS, "pbftv_register_signing_keys has not been called");
+  return run_sharded(ctx, n, [&](Device& d, Shard s) -> int {
+    std::lock_guard<std::mutex> lk(d.mu);
+    HIP_TRY(hipSetDevice(d.id));
+    const uint64_t m = s.hi - s.lo;
+    const int rc = [&]() -> int {
+      HIP_TRY(d.hashes.ensure(32 * m + 64));
+      HIP_TRY(d.key_idx.ensure(4 * m + 64));
+      HIP_TRY(hipMemcpyAsync(d.hashes.p, hashes + 32 * s.lo, 32 * m, hipMemcpyHostToDevice, d.stream));
+      HIP_TRY(hipMemcpyAsync(d.key_idx.p, skey_idx + s.lo, 4 * m, hipMemcpyHostToDevice, d.stream));
+      if (out_rs) {
+        HIP_TRY(d.sigs.ensure(64 * m + 64));
+        HIP_TRY(d.bitmap.ensure((m + 7) / 8 + 8));
+        const int r = sign_on_device(d, d.hashes.as<uint8_t>(), d.key_idx.as<uint32_t>(), m, d.sigs.as<uint8_t>(),
+                                     d.bitmap.as<uint8_t>(), d.stream);
+        if (r != PBFTV_OK) return r;
+        HIP_TRY(hipMemcpyAsync(out_rs + 64 * s.lo, d.sigs.p, 64 * m, hipMemcpyDeviceToHost, d.stream));
+        if (out_ok)
+          HIP_TRY(hipMemcpyAsync(out_ok + s.lo / 8, d.bitmap.p, (m + 7) / 8, hipMemcpyDeviceToHost, d.stream));
+      } else {
+        HIP_TRY(d.sign.der.ensure(72 * m + 64));
+        HIP_TRY(d.sign.der_len.ensure(4 * m + 64));
+        const int r = sign_der_on_device(d, d.hashes.as<uint8_t>(), d.key_idx.as<uint32_t>(), m,
+                                         d.sign.der.as<uint8_t>(), d.sign.der_len.as<uint32_t>(), d.stream);
+        if (r != PBFTV_OK) return r;
+        HIP_TRY(hipMemcpyAsync(out_der + 72 * s.lo, d.sign.der.p, 72 * m, hipMemcpyDeviceToHost, d.stream));
+        HIP_TRY(hipMemcpyAsync(out_der_len + s.lo, d.sign.der_len.p, 4 * m, hipMemcpyDeviceToHost, d.stream));
+      }
+      HIP_TRY(hipStreamSynchronize(d.stream));
+      return PBFTV_OK;
+    }();
+    if (rc != PBFTV_OK) (void)hipStreamSynchronize(d.stream);  // (fail() has kept the first error's message)
+    return rc;
+  });
+}
+
+int pbftv_ecdsa_p256_sign_batch(pbftv_ctx* ctx, const uint8_t* hashes, const uint32_t* skey_idx, uint64_t n,
+                                uint8_t* out_sig_rs, uint8_t* out_ok_bitmap) {
+  if (n && n >> 32 == 0 && !out_sig_rs) return fail(PBFTV_EINVAL, "null buffer");
+  return sign_host(ctx, hashes, skey_idx, n, out_sig_rs, out_ok_bitmap, nullptr, nullptr);
+}
+
+int pbftv_ecdsa_p256_sign_der_batch(pbftv_ctx* ctx, const uint8_t* hashes, const uint32_t* skey_idx, uint64_t n,
+                                    uint8_t* out_der, uint32_t* out_der_len) {
+  return sign_host(ctx, hashes, skey_idx, n, nullptr, nullptr, out_der, out_der_len);
+}
+
 int pbftv_qc_stamps(pbftv_ctx* ctx, int dev, uint64_t out[8]) {
   Device* d = dev_of(ctx, dev);
   if (!d || !out) return fail(PBFTV_EINVAL, "bad context, device index or out pointer");
@@ -3412,6 +3689,96 @@ int pbftv_digest_reply_batch(pbftv_ctx* ctx, uint64_t n, const int64_t* view_ids
   return pbftv_flush_replies(ctx, n, view_ids, timestamps, client_ids, client_id_off, client_id_len, node_ids,
                              node_id_off, node_id_len, results, result_off, result_len, nullptr, nullptr, out_digests,
                              nullptr);
+}
+
+// Replies signed where they are digested: encode, hash and sign in one round
+// trip per device, the digests never leaving HBM in between (the flushes'
+// pattern with the signer in the verify's place).  der: slots and lengths
+// instead of r||s rows and ok bits.
+static int sign_replies_by(pbftv_ctx* ctx, uint64_t n, const int64_t* view_ids, const int64_t* timestamps,
+                           const uint8_t* client_ids, const uint64_t* client_id_off, const uint32_t* client_id_len,
+                           const uint8_t* node_ids, const uint64_t* node_id_off, const uint32_t* node_id_len,
+                           const uint8_t* results, const uint64_t* result_off, const uint32_t* result_len,
+                           const uint32_t* skey_idx, uint8_t* out_digests, uint8_t* out_sig_rs, uint8_t* out_ok_bitmap,
+                           uint8_t* out_der, uint32_t* out_der_len) {
+  if (!ctx) return fail(PBFTV_EINVAL, "ctx is null");
+  if (n >> 32) return fail(PBFTV_EINVAL, "n must be below 2^32");
+  if (n == 0) return PBFTV_OK;
+  if (!view_ids || !timestamps || !client_id_off || !client_id_len || !node_id_off || !node_id_len || !result_off ||
+      !result_len || !skey_idx || !(out_sig_rs || (out_der && out_der_len)))
+    return fail(PBFTV_EINVAL, "null buffer");
+  if (!sign_keys_ready(ctx)) return fail(PBFTV_ENOSIGNKEYS, "pbftv_register_signing_keys has not been called");
+  return run_sharded(ctx, n, [&](Device& d, Shard s) -> int {
+    const uint64_t m = s.hi - s.lo;
+    Packer p;
+    uint64_t pre = 0;
+    const size_t o_slot = p.add_owned(slots(s.lo, s.hi, [&](uint64_t i) {
+      return pbftv::gojson::reply_bound(client_id_len[i], node_id_len[i], result_len[i]);
+    }, &pre));
+    const size_t o_view = p.add(view_ids + s.lo, 8 * m), o_ts = p.add(timestamps + s.lo, 8 * m);
+    const auto cid = p.add_str(client_ids, client_id_off, client_id_len, s.lo, s.hi);
+    const auto nid = p.add_str(node_ids, node_id_off, node_id_len, s.lo, s.hi);
+    const auto res = p.add_str(results, result_off, result_len, s.lo, s.hi);
+    const size_t o_key = p.add(skey_idx + s.lo, 4 * m);
+    std::lock_guard<std::mutex> lk(d.mu);
+    HIP_TRY(hipSetDevice(d.id));
+    int rc = upload(d, p);
+    if (rc != PBFTV_OK) return rc;
+    const pbftv::ReplyCols c{at<int64_t>(d, o_view), at<int64_t>(d, o_ts), str_col(d, cid), str_col(d, nid),
+                             str_col(d, res)};
+    const uint64_t* slot = at<uint64_t>(d, o_slot);
+    rc = [&]() -> int {
+      int r = encode_and_hash(d, m, slot, pre, [&] {
+        return pbftv::launch_gojson_reply(c, m, slot, d.data.as<uint8_t>(), d.lengths.as<uint32_t>(), d.stream);
+      });
+      if (r != PBFTV_OK) return r;
+      if (out_sig_rs) {
+        HIP_TRY(d.sigs.ensure(64 * m + 64));
+        HIP_TRY(d.bitmap.ensure((m + 7) / 8 + 8));
+        r = sign_on_device(d, d.digests.as<uint8_t>(), at<uint32_t>(d, o_key), m, d.sigs.as<uint8_t>(),
+                           d.bitmap.as<uint8_t>(), d.stream);
+        if (r != PBFTV_OK) return r;
+        HIP_TRY(hipMemcpyAsync(out_sig_rs + 64 * s.lo, d.sigs.p, 64 * m, hipMemcpyDeviceToHost, d.stream));
+        if (out_ok_bitmap)
+          HIP_TRY(hipMemcpyAsync(out_ok_bitmap + s.lo / 8, d.bitmap.p, (m + 7) / 8, hipMemcpyDeviceToHost, d.stream));
+      } else {
+        HIP_TRY(d.sign.der.ensure(72 * m + 64));
+        HIP_TRY(d.sign.der_len.ensure(4 * m + 64));
+        r = sign_der_on_device(d, d.digests.as<uint8_t>(), at<uint32_t>(d, o_key), m, d.sign.der.as<uint8_t>(),
+                               d.sign.der_len.as<uint32_t>(), d.stream);
+        if (r != PBFTV_OK) return r;
+        HIP_TRY(hipMemcpyAsync(out_der + 72 * s.lo, d.sign.der.p, 72 * m, hipMemcpyDeviceToHost, d.stream));
+        HIP_TRY(hipMemcpyAsync(out_der_len + s.lo, d.sign.der_len.p, 4 * m, hipMemcpyDeviceToHost, d.stream));
+      }
+      if (out_digests)
+        HIP_TRY(hipMemcpyAsync(out_digests + 32 * s.lo, d.digests.p, 32 * m, hipMemcpyDeviceToHost, d.stream));
+      HIP_TRY(hipStreamSynchronize(d.stream));
+      return PBFTV_OK;
+    }();
+    if (rc != PBFTV_OK) (void)hipStreamSynchronize(d.stream);  // (the arena's staging is reused by the next call)
+    return rc;
+  });
+}
+
+int pbftv_sign_replies(pbftv_ctx* ctx, uint64_t n, const int64_t* view_ids, const int64_t* timestamps,
+                       const uint8_t* client_ids, const uint64_t* client_id_off, const uint32_t* client_id_len,
+                       const uint8_t* node_ids, const uint64_t* node_id_off, const uint32_t* node_id_len,
+                       const uint8_t* results, const uint64_t* result_off, const uint32_t* result_len,
+                       const uint32_t* skey_idx, uint8_t* out_digests, uint8_t* out_sig_rs, uint8_t* out_ok_bitmap) {
+  if (ctx && n && n >> 32 == 0 && !out_sig_rs) return fail(PBFTV_EINVAL, "null buffer");
+  return sign_replies_by(ctx, n, view_ids, timestamps, client_ids, client_id_off, client_id_len, node_ids,
+                         node_id_off, node_id_len, results, result_off, result_len, skey_idx, out_digests, out_sig_rs,
+                         out_ok_bitmap, nullptr, nullptr);
+}
+
+int pbftv_sign_replies_der(pbftv_ctx* ctx, uint64_t n, const int64_t* view_ids, const int64_t* timestamps,
+                           const uint8_t* client_ids, const uint64_t* client_id_off, const uint32_t* client_id_len,
+                           const uint8_t* node_ids, const uint64_t* node_id_off, const uint32_t* node_id_len,
+                           const uint8_t* results, const uint64_t* result_off, const uint32_t* result_len,
+                           const uint32_t* skey_idx, uint8_t* out_digests, uint8_t* out_der, uint32_t* out_der_len) {
+  return sign_replies_by(ctx, n, view_ids, timestamps, client_ids, client_id_off, client_id_len, node_ids,
+                         node_id_off, node_id_len, results, result_off, result_len, skey_idx, out_digests, nullptr,
+                         nullptr, out_der, out_der_len);
 }
 
 static int flush_preprepares_sig(pbftv_ctx* ctx, uint64_t n, const int64_t* view_ids, const int64_t* sequence_ids,

@@ -23,6 +23,7 @@ PBFTV_ENODEV = -2
 PBFTV_EDEVICE = -3
 PBFTV_ENOMEM = -4
 PBFTV_ENOKEYS = -5
+PBFTV_ENOSIGNKEYS = -6
 
 # key formats of the *_wirekey entry points (include/pbftv.h PBFTV_KEY_*)
 KEY_XY = 0                 # X||Y, 64 B
@@ -172,6 +173,17 @@ def lib() -> ctypes.CDLL:
                                              [_vp] * 4),
         "pbftv_flush_replies_wirekey_der": (ctypes.c_int, [_vp, ctypes.c_uint64] + [_vp] * 15 + [ctypes.c_int] +
                                             [_vp] * 2),
+        "pbftv_sign_kernel_time_ms": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double),
+                                                     ctypes.POINTER(ctypes.c_uint64)]),
+        "pbftv_register_signing_keys": (ctypes.c_int, [_vp, _vp, ctypes.c_uint32, _vp]),
+        "pbftv_ecdsa_p256_sign_batch": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint64, _vp, _vp]),
+        "pbftv_ecdsa_p256_sign_batch_dev": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, ctypes.c_uint64, _vp, _vp,
+                                                           _vp]),
+        "pbftv_ecdsa_p256_sign_der_batch": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint64, _vp, _vp]),
+        "pbftv_ecdsa_p256_sign_der_batch_dev": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, ctypes.c_uint64, _vp, _vp,
+                                                               _vp]),
+        "pbftv_sign_replies": (ctypes.c_int, [_vp, ctypes.c_uint64] + [_vp] * 15),
+        "pbftv_sign_replies_der": (ctypes.c_int, [_vp, ctypes.c_uint64] + [_vp] * 15),
         "pbftv_qc_verify": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_uint64, ctypes.c_uint32, _vp,
                                            ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_int)]),
     }
@@ -358,6 +370,7 @@ K_ECDSA_WAVE = 3
 K_GOJSON = 4
 K_ECDSA_VARBASE = 5
 K_ECDSA_DER = 6  # (read through Verifier.der_kernel_time_ms; kernel_time_ms takes 0..5)
+K_ECDSA_SIGN = 7  # (read through Verifier.sign_kernel_time_ms, per stage)
 
 
 class RequestColumns:
@@ -660,6 +673,14 @@ class Verifier:
         _check(self._L.pbftv_der_kernel_time_ms(self._h, dev, ctypes.byref(ms), ctypes.byref(cnt)))
         return ms.value, cnt.value
 
+    def sign_kernel_time_ms(self, dev: int, stage: int = 0):
+        """pbftv_sign_kernel_time_ms: (ms, launches) of the sign kernels, timing id PBFTV_K_ECDSA_SIGN;
+        stage 0 = all, 1 = nonce, 2 = comb, 3 = tail, 4 = DER writer"""
+        ms = ctypes.c_double()
+        cnt = ctypes.c_uint64()
+        _check(self._L.pbftv_sign_kernel_time_ms(self._h, dev, stage, ctypes.byref(ms), ctypes.byref(cnt)))
+        return ms.value, cnt.value
+
     def reset_kernel_times(self):
         _check(self._L.pbftv_reset_kernel_times(self._h))
 
@@ -919,6 +940,73 @@ class Verifier:
         valid = np.zeros(1, np.uint8)
         _check(self._L.pbftv_set_key(self._h, index, pub.ctypes.data, valid.ctypes.data))
         return bool(valid[0])
+
+    # ---- signing (RFC 6979 ECDSA-P256; the set is independent of register_keys')
+    def register_signing_keys(self, priv: np.ndarray) -> np.ndarray:
+        """pbftv_register_signing_keys: k private keys, 32 big-endian bytes each; their validity."""
+        priv = np.ascontiguousarray(priv, np.uint8).reshape(-1, 32)
+        k = priv.shape[0]
+        valid = np.zeros(max(k, 1), np.uint8)
+        _check(self._L.pbftv_register_signing_keys(self._h, priv.ctypes.data, k, valid.ctypes.data))
+        return valid[:k].astype(bool)
+
+    def sign_batch(self, hashes: np.ndarray, skey_idx: np.ndarray):
+        """pbftv_ecdsa_p256_sign_batch: (r||s rows (n, 64), ok (n,) bool)."""
+        hashes = np.ascontiguousarray(hashes, np.uint8).reshape(-1, 32)
+        skey_idx = np.ascontiguousarray(skey_idx, np.uint32)
+        n = hashes.shape[0]
+        assert skey_idx.shape[0] == n
+        sig = np.zeros((max(n, 1), 64), np.uint8)
+        bm = np.zeros((n + 7) // 8 + 1, np.uint8)
+        _check(self._L.pbftv_ecdsa_p256_sign_batch(self._h, hashes.ctypes.data, skey_idx.ctypes.data, n,
+                                                   sig.ctypes.data, bm.ctypes.data))
+        return sig[:n], bitmap_to_bool(bm, n)
+
+    def sign_batch_dev(self, dev: int, d_hashes: int, d_skey_idx: int, n: int, d_sigs: int, d_ok_bitmap: int | None,
+                       stream: int | None = None):
+        _check(self._L.pbftv_ecdsa_p256_sign_batch_dev(self._h, dev, d_hashes, d_skey_idx, n, d_sigs, d_ok_bitmap,
+                                                       stream))
+
+    def sign_der_batch(self, hashes: np.ndarray, skey_idx: np.ndarray):
+        """pbftv_ecdsa_p256_sign_der_batch: (72-byte slots (n, 72), lengths (n,); 0 = not signed)."""
+        hashes = np.ascontiguousarray(hashes, np.uint8).reshape(-1, 32)
+        skey_idx = np.ascontiguousarray(skey_idx, np.uint32)
+        n = hashes.shape[0]
+        assert skey_idx.shape[0] == n
+        der = np.zeros((max(n, 1), 72), np.uint8)
+        ln = np.zeros(max(n, 1), np.uint32)
+        _check(self._L.pbftv_ecdsa_p256_sign_der_batch(self._h, hashes.ctypes.data, skey_idx.ctypes.data, n,
+                                                       der.ctypes.data, ln.ctypes.data))
+        return der[:n], ln[:n]
+
+    def sign_der_batch_dev(self, dev: int, d_hashes: int, d_skey_idx: int, n: int, d_der: int, d_der_len: int,
+                           stream: int | None = None):
+        _check(self._L.pbftv_ecdsa_p256_sign_der_batch_dev(self._h, dev, d_hashes, d_skey_idx, n, d_der, d_der_len,
+                                                           stream))
+
+    def sign_replies(self, cols: "ReplyColumns", skey_idx: np.ndarray, digests: bool = True):
+        """pbftv_sign_replies: (digests | None, r||s rows, ok)."""
+        n = cols.n
+        skey_idx = np.ascontiguousarray(skey_idx, np.uint32)
+        assert skey_idx.shape[0] == n
+        out_d = np.zeros((max(n, 1), 32), np.uint8) if digests else None
+        sig = np.zeros((max(n, 1), 64), np.uint8)
+        bm = np.zeros((n + 7) // 8 + 1, np.uint8)
+        _check(self._L.pbftv_sign_replies(self._h, n, *cols.args(), skey_idx.ctypes.data, _ptr(out_d),
+                                          sig.ctypes.data, bm.ctypes.data))
+        return (out_d[:n] if out_d is not None else None, sig[:n], bitmap_to_bool(bm, n))
+
+    def sign_replies_der(self, cols: "ReplyColumns", skey_idx: np.ndarray, digests: bool = True):
+        """pbftv_sign_replies_der: (digests | None, 72-byte slots, lengths)."""
+        n = cols.n
+        skey_idx = np.ascontiguousarray(skey_idx, np.uint32)
+        assert skey_idx.shape[0] == n
+        out_d = np.zeros((max(n, 1), 32), np.uint8) if digests else None
+        der = np.zeros((max(n, 1), 72), np.uint8)
+        ln = np.zeros(max(n, 1), np.uint32)
+        _check(self._L.pbftv_sign_replies_der(self._h, n, *cols.args(), skey_idx.ctypes.data, _ptr(out_d),
+                                              der.ctypes.data, ln.ctypes.data))
+        return (out_d[:n] if out_d is not None else None, der[:n], ln[:n])
 
     def table_config(self):
         """(G window bits, key window bits, table bytes per device)."""
