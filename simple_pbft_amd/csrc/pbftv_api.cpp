@@ -30,7 +30,9 @@
 #include "../../include/pbftv.h"
 #include "gojson.h"
 #include "gojson_enc.h"
+#include "host/kernel_timers.h"
 #include "host/pending_frees.h"
+#include "host/scratch_order.h"
 #include "der.h"
 #include "kernels.h"
 
@@ -214,6 +216,15 @@ struct VerifyScratch {
   }
 };
 
+// the event operations of the timing table (host/kernel_timers.h)
+struct TimerOps {
+  static hipError_t create(hipEvent_t* e) { return hipEventCreate(e); }
+  static hipError_t destroy(hipEvent_t e) { return hipEventDestroy(e); }
+  static hipError_t record(hipEvent_t e, hipStream_t st) { return hipEventRecord(e, st); }
+  static hipError_t synchronize(hipEvent_t e) { return hipEventSynchronize(e); }
+  static hipError_t elapsed(float* ms, hipEvent_t a, hipEvent_t b) { return hipEventElapsedTime(ms, a, b); }
+};
+
 struct Device {
   int id = -1;
   hipStream_t stream = nullptr;
@@ -320,13 +331,11 @@ struct Device {
   std::vector<hipEvent_t> spare_ev;
   uint64_t ev_created = 0;  // marks ever created: each is in one pending free or in spare_ev (pbftv_lib_counters)
   std::atomic<uint64_t> sorted_batches{0};  // lane-path batches that took the key order
-  // Device scratch (rec, prefix, ksort, okb, order_scratch) is shared by
-  // calls on d.stream and on caller streams (the *_dev entry points).  The
-  // mutex orders the enqueues; this event orders the execution: a call on a
-  // different stream than the last scratch user first waits for it.
-  hipEvent_t scratch_ev = nullptr;
-  hipStream_t scratch_st = nullptr;
-  bool scratch_lazy = false;  // scratch_st == stream: scratch_ev not yet recorded for its last use
+  // Device scratch (rec, prefix, ksort, okb, order_scratch, der.rs, the sign
+  // buffers) is shared by calls on d.stream and on caller streams (the *_dev
+  // entry points).  The mutex orders the enqueues; this orders the execution
+  // (host/scratch_order.h; taken through a ScratchLease, below)
+  pbftv::ScratchOrder<hipStream_t, hipEvent_t> scratch;
   // streams made by pbftv_stream_create own their verify scratch: ECDSA
   // verifies on two such streams run concurrently (batch j + 1's scalar stage
   // in the wave slots batch j's comb leaves free) instead of queueing on d.vs
@@ -336,45 +345,36 @@ struct Device {
   static constexpr size_t kOwnQueues = 8;
   std::set<hipStream_t> own_queue;
   // caller streams the library did not create that a wave-path verify (no
-  // device scratch, so no scratch_ev fence) was enqueued on since the last key
+  // device scratch, so no scratch fence) was enqueued on since the last key
   // change: an event recorded after each such enqueue (events stay valid when
   // the caller destroys its stream); ctx_quiesce waits for them all
   std::map<hipStream_t, hipEvent_t> reader_ev;
-  // kernel timing (events recorded around launches while ctx timing is on)
+  // kernel timing (events recorded around launches while ctx timing is on;
+  // host/kernel_timers.h): one table, a slot per timing id 0..6
+  // (PBFTV_K_ECDSA_SCALARS .. PBFTV_K_ECDSA_DER), then one per sign stage
+  // (id PBFTV_K_ECDSA_SIGN: nonce, comb, tail, DER writer)
   const bool* timing = nullptr;
   const std::atomic<uint64_t>* wave_max = nullptr;  // the context's latency-path threshold
-  static constexpr int kKernels = 6;  // PBFTV_K_*
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> pending[kKernels];
-  double acc_ms[kKernels] = {0, 0, 0, 0, 0, 0};
-  uint64_t launches[kKernels] = {0, 0, 0, 0, 0, 0};
+  static constexpr int kKernels = 6;     // what pbftv_kernel_time_ms answers for
+  static constexpr int kSignStages = pbftv::kSignStages + 1;  // slots PBFTV_K_ECDSA_SIGN .. + 3
+  pbftv::KernelTimers<hipEvent_t, PBFTV_K_ECDSA_SIGN + kSignStages, TimerOps> timers;
   // DER signatures (der_kernels.hip): the r||s column the normaliser writes for
   // the *_der verifies and flushes (64 B per signature; one per device, every
-  // use ordered by the scratch event, also on streams that own a
-  // VerifyScratch) and timing id PBFTV_K_ECDSA_DER.  Kept apart from
-  // VerifyScratch and the arrays above, after every other member: no call
-  // that existed before the DER forms reads or writes any of it.
+  // use ordered by the scratch order, also on streams that own a
+  // VerifyScratch).
   struct Der {
     DevBuf rs;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
-    double acc_ms = 0;
-    uint64_t launches = 0;
   } der;
   // Signing (p256_sign.hip): the private keys (8 LE words each, then one
   // validity word each; wiped with zeros before the buffer is freed, replaced
   // or the context closes), the stage records, the r||s rows and ok bits the
   // DER forms and pbftv_sign_replies sign into (one of each per device, every
-  // use ordered by the scratch event like Device::der.rs), and timing id
-  // PBFTV_K_ECDSA_SIGN per stage (nonce, comb, tail, DER writer).  After every
-  // other member, as Device::der: no call that existed before reads any of it.
+  // use ordered by the scratch order like Device::der.rs).
   struct Sign {
     DevBuf keys;
     uint32_t nkeys = 0;
     bool have = false;
     DevBuf rec, rs, okb, der, der_len;
-    static constexpr int kStages = 4;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> pending[kStages];
-    double acc_ms[kStages] = {0, 0, 0, 0};
-    uint64_t launches[kStages] = {0, 0, 0, 0};
   } sign;
 };
 
@@ -430,71 +430,38 @@ hipError_t own_queue_stream(int dev, bool want_own, hipStream_t* st, bool* own) 
   return hipStreamCreateWithFlags(st, hipStreamNonBlocking);
 }
 
-// before / after enqueueing work that uses the device scratch on stream st.
-// A caller stream's use is fenced by an event recorded right after it.  The
-// library's own stream (d.stream, which lives as long as the context) is fenced
-// lazily: its event is recorded only when another stream next wants the
-// scratch -- recording later on the same stream covers at least the scratch
-// work -- so back-to-back calls on d.stream queue no marker between batches
-// (each marker costs the GPU a ~6 us gap between kernels, rocprof timeline).
-hipError_t scratch_acquire(Device& d, hipStream_t st) {
-  if (d.scratch_st == nullptr || d.scratch_st == st) return hipSuccess;
-  if (d.scratch_lazy) {
-    if (!d.scratch_ev) {
-      hipError_t e = hipEventCreateWithFlags(&d.scratch_ev, hipEventDisableTiming);
+// One use of the device scratch on stream st (d.mu held): acquire() before the
+// first enqueue, release() on the success path; every other exit releases in
+// the destructor.  The state machine, and why d.stream records no event
+// between its own batches (the lazy fence), is host/scratch_order.h.
+struct ScratchOps {
+  static hipError_t record(hipEvent_t& ev, hipStream_t st) {
+    if (!ev) {
+      hipError_t e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
       if (e != hipSuccess) return e;
     }
-    hipError_t e = hipEventRecord(d.scratch_ev, d.scratch_st);
-    if (e != hipSuccess) return e;
-    d.scratch_lazy = false;
+    return hipEventRecord(ev, st);
   }
-  return hipStreamWaitEvent(st, d.scratch_ev, 0);
+  static hipError_t wait(hipStream_t st, hipEvent_t ev) { return hipStreamWaitEvent(st, ev, 0); }
+};
+using ScratchLease = pbftv::ScratchLease<hipStream_t, hipEvent_t, ScratchOps>;
+
+// the verify scratch of a batch on st: the stream's own (pbftv_stream_create;
+// `own` when the caller already holds one), else null -- d.vs, under a lease
+VerifyScratch* own_scratch(Device& d, hipStream_t st, VerifyScratch* own = nullptr) {
+  if (own) return own;
+  auto it = d.stream_scratch.find(st);
+  return it != d.stream_scratch.end() ? it->second.get() : nullptr;
 }
 
-hipError_t scratch_release(Device& d, hipStream_t st) {
-  d.scratch_st = st;
-  d.scratch_lazy = st == d.stream;
-  if (d.scratch_lazy) return hipSuccess;
-  if (!d.scratch_ev) {
-    hipError_t e = hipEventCreateWithFlags(&d.scratch_ev, hipEventDisableTiming);
-    if (e != hipSuccess) return e;
-  }
-  return hipEventRecord(d.scratch_ev, st);
-}
-
-// record start/stop events around one launch when timing is enabled
+// record start/stop events around one launch when timing is enabled (slot: a
+// timing id up to PBFTV_K_ECDSA_DER, or PBFTV_K_ECDSA_SIGN + the sign stage)
 template <class F>
-hipError_t timed(Device& d, int k, hipStream_t st, F launch) {
-  if (!d.timing || !*d.timing) return launch();
-  hipEvent_t a, b;
-  hipError_t e = hipEventCreate(&a);
-  if (e != hipSuccess) return e;
-  e = hipEventCreate(&b);
-  if (e != hipSuccess) return e;
-  (void)hipEventRecord(a, st);
-  e = launch();
-  (void)hipEventRecord(b, st);
-  d.pending[k].push_back({a, b});
-  return e;
+hipError_t timed(Device& d, int slot, hipStream_t st, F launch) {
+  return d.timers.timed(d.timing && *d.timing, slot, st, launch);
 }
 
-hipError_t collect_times(Device& d) {
-  for (int k = 0; k < Device::kKernels; ++k) {
-    for (auto& pr : d.pending[k]) {
-      hipError_t e = hipEventSynchronize(pr.second);
-      if (e != hipSuccess) return e;
-      float ms = 0;
-      e = hipEventElapsedTime(&ms, pr.first, pr.second);
-      if (e != hipSuccess) return e;
-      d.acc_ms[k] += ms;
-      d.launches[k] += 1;
-      (void)hipEventDestroy(pr.first);
-      (void)hipEventDestroy(pr.second);
-    }
-    d.pending[k].clear();
-  }
-  return hipSuccess;
-}
+hipError_t collect_times(Device& d) { return d.timers.collect(); }
 
 // ---- the armed latency kernel (verify_kernels.h k_ecdsa_wave_armed) ----
 using pbftv::ArmArgs;
@@ -652,7 +619,7 @@ hipError_t qc_disarm(Device& d) {
 // leave (qc_disarm), then its own streams drain, and every caller stream it
 // was given: streams from pbftv_stream_create are known (stream_scratch); any
 // other caller stream shares the device scratch, whose last use is fenced by
-// scratch_ev, and every use waited for the one before it (scratch_acquire).
+// the scratch order's event, and every use waited for the one before it.
 // Other contexts on the GPU are not waited for: their kernels read their own
 // key tables, and a G table is never rewritten in place (a new width is a new
 // table).  Frees inside the key change still quiesce the GPU (DevBuf).
@@ -661,7 +628,7 @@ hipError_t ctx_quiesce(Device& d) {
   for (hipStream_t s : {d.stream, d.stream2, d.cstream, d.lstream})
     if (s) HIP_TRY_E(hipStreamSynchronize(s));
   for (auto& kv : d.stream_scratch) HIP_TRY_E(hipStreamSynchronize(kv.first));
-  if (d.scratch_st && d.scratch_st != d.stream && d.scratch_ev) HIP_TRY_E(hipEventSynchronize(d.scratch_ev));
+  if (hipEvent_t ev = d.scratch.caller_fence()) HIP_TRY_E(hipEventSynchronize(ev));
   for (auto& kv : d.reader_ev) HIP_TRY_E(hipEventSynchronize(kv.second));
   for (auto& kv : d.reader_ev) (void)hipEventDestroy(kv.second);
   d.reader_ev.clear();
@@ -1101,6 +1068,48 @@ int run_sharded(pbftv_ctx* ctx, uint64_t n, Fn fn) {
 
 hipStream_t pick_stream(Device& d, void* stream) { return stream ? reinterpret_cast<hipStream_t>(stream) : d.stream; }
 
+// One shard's round trip of a host form on d.stream: d.mu taken, the device
+// current, body() -- copies in, the device form, copies out -- and d.stream
+// synchronised, also after a body that failed: no asynchronous copy still reads
+// or writes the caller's memory, or staging the next call reuses, when this
+// returns (fail() has kept the first error's message).
+template <class Body>
+int shard_round_trip(Device& d, Body body) {
+  std::lock_guard<std::mutex> lk(d.mu);
+  HIP_TRY(hipSetDevice(d.id));
+  const int rc = body();
+  if (rc != PBFTV_OK) (void)hipStreamSynchronize(d.stream);
+  else HIP_TRY(hipStreamSynchronize(d.stream));
+  return rc;
+}
+
+// a column of the shard into its device buffer (grown to bytes + slack), on d.stream
+hipError_t copy_in(Device& d, DevBuf& b, const void* src, size_t bytes, size_t slack) {
+  HIP_TRY_E(b.ensure(bytes + slack));
+  return hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, d.stream);
+}
+
+// Items [lo, hi) of a string column: the span [a, b) of the blob they use --
+// of each string only its first `clip` bytes (a DER column: the normaliser
+// reads no more of an encoding, der.h) -- and, in `rebased`, their offsets
+// from a (an empty string's: 0).  No string with a byte: a == b == 0.
+struct StrSpan {
+  uint64_t a, b;
+};
+StrSpan str_span(const uint64_t* off, const uint32_t* len, uint64_t lo, uint64_t hi, uint32_t clip,
+                 std::vector<uint64_t>& rebased) {
+  StrSpan s{UINT64_MAX, 0};
+  rebased.resize(hi - lo);
+  for (uint64_t i = lo; i < hi; ++i)
+    if (len[i]) {
+      s.a = std::min(s.a, off[i]);
+      s.b = std::max(s.b, off[i] + std::min(len[i], clip));
+    }
+  if (s.a > s.b) s.a = s.b = 0;
+  for (uint64_t i = lo; i < hi; ++i) rebased[i - lo] = len[i] ? off[i] - s.a : 0;
+  return s;
+}
+
 // ---- message batches: column inputs packed for ONE host->device copy ----
 // Host segments are copied (16-B aligned) into the device's pinned staging
 // buffer, then to its device arena with a single hipMemcpyAsync.
@@ -1127,26 +1136,17 @@ struct Packer {
   struct Str {
     size_t data, off, len;
   };
-  // clip: only the first `clip` bytes of each string count toward the span
-  // (a DER column: the normaliser reads no more of an encoding, der.h; the
-  // lengths go to the device as they are)
+  // clip: as in str_span (the lengths go to the device as they are)
   Str add_str(const uint8_t* data, const uint64_t* off, const uint32_t* len, uint64_t lo, uint64_t hi,
               uint32_t clip = UINT32_MAX) {
-    uint64_t a = UINT64_MAX, b = 0;
-    for (uint64_t i = lo; i < hi; ++i)
-      if (len[i]) {
-        a = std::min(a, off[i]);
-        b = std::max(b, off[i] + std::min(len[i], clip));
-      }
-    if (a > b) a = b = 0;
-    if (b > a && data == nullptr) {
-      null_blob = true;
-      a = b = 0;
+    std::vector<uint64_t> r;
+    StrSpan sp = str_span(off, len, lo, hi, clip, r);
+    if (sp.b > sp.a && data == nullptr) {
+      null_blob = true;  // (upload refuses the whole pack)
+      sp.b = sp.a;
     }
-    std::vector<uint64_t> r(hi - lo);
-    for (uint64_t i = lo; i < hi; ++i) r[i - lo] = len[i] ? off[i] - a : 0;
     Str s;
-    s.data = add(b > a ? data + a : nullptr, b - a);
+    s.data = add(sp.b > sp.a ? data + sp.a : nullptr, sp.b - sp.a);
     s.off = add_owned(std::move(r));
     s.len = add(len + lo, 4 * (hi - lo));
     return s;
@@ -1314,6 +1314,7 @@ int pbftv_open(pbftv_ctx** out, uint32_t device_mask) {
       dev->wave_max = &ctx->wave_max;
       HIP_TRY(hipSetDevice(d));
       HIP_TRY(hipStreamCreateWithFlags(&dev->stream, hipStreamNonBlocking));
+      dev->scratch.set_own(dev->stream);
       ctx->devs.push_back(std::move(dev));
     }
   }
@@ -1338,6 +1339,7 @@ void pbftv_close(pbftv_ctx* ctx) {
     // and their scratch: they finish before anything below is freed
     for (auto& kv : d->stream_scratch) (void)hipStreamSynchronize(kv.first);
     (void)collect_times(*d);
+    d->timers.drop();  // (what could not be read: no event pair outlives the context)
     (void)sign_wipe_keys(*d);  // zeros over the private keys before their memory goes back
     for (DevBuf* b : {&d->sign.keys, &d->sign.rec, &d->sign.rs, &d->sign.okb, &d->sign.der, &d->sign.der_len})
       b->release();
@@ -1354,7 +1356,7 @@ void pbftv_close(pbftv_ctx* ctx) {
       b->release();  // explicit, with this device current (the destructors are a backstop)
     d->cuflag_ready.store(nullptr);
     for (HostBuf* b : {&d->stage, &d->mstage, &d->mout, &d->sstage}) b->release();
-    if (d->scratch_ev) (void)hipEventDestroy(d->scratch_ev);
+    if (d->scratch.event()) (void)hipEventDestroy(d->scratch.event());
     for (auto& kv : d->reader_ev) (void)hipEventDestroy(kv.second);
     d->reader_ev.clear();
     if (d->stream2) {
@@ -1441,6 +1443,30 @@ static Device* dev_of(pbftv_ctx* ctx, int dev) {
   return ctx->devs[dev].get();
 }
 
+static int bad_dev() { return fail(PBFTV_EINVAL, "bad context or device index"); }
+static int n_below_2_32(uint64_t n) { return n >> 32 ? fail(PBFTV_EINVAL, "n must be below 2^32") : PBFTV_OK; }
+
+// The prologue of a *_dev entry point, in two steps: an entry point checks its
+// own arguments (and returns for n == 0) in between, before any lock or HIP call.
+//   args(ctx, dev)   the context and the device index
+//   enter(stream)    d.mu taken (until the DevEntry goes), the device current, the stream picked
+namespace {
+struct DevEntry {
+  Device* dev = nullptr;
+  hipStream_t st = nullptr;
+  std::unique_lock<std::mutex> lk;
+  int args(pbftv_ctx* ctx, int i) { return (dev = dev_of(ctx, i)) ? PBFTV_OK : bad_dev(); }
+  int args(pbftv_ctx* ctx, int i, uint64_t n) { return (dev = dev_of(ctx, i)) ? n_below_2_32(n) : bad_dev(); }
+  int enter(void* stream) {
+    Device& d = *dev;
+    lk = std::unique_lock<std::mutex>(d.mu);
+    HIP_TRY(hipSetDevice(d.id));
+    st = pick_stream(d, stream);
+    return PBFTV_OK;
+  }
+};
+}  // namespace
+
 // The device pool of pbftv_dev_alloc: memory is never returned to the
 // driver while the context lives (release threshold: unlimited), so a free
 // is bookkeeping, not hipFree (which waits for every kernel on the GPU, the
@@ -1472,8 +1498,8 @@ static hipError_t dev_pool_ready(Device& d) {
 // for on the host here, as hipFree's implicit synchronisation would -- only
 // that work, not the whole GPU.
 static hipError_t defer_free(Device& d, void* p) {
-  if (d.scratch_st && d.scratch_st != d.stream && !d.stream_scratch.count(d.scratch_st) && d.scratch_ev)
-    HIP_TRY_E(hipEventSynchronize(d.scratch_ev));
+  if (hipEvent_t ev = d.scratch.caller_fence())
+    if (!d.stream_scratch.count(d.scratch.last())) HIP_TRY_E(hipEventSynchronize(ev));
   for (auto& kv : d.reader_ev) HIP_TRY_E(hipEventSynchronize(kv.second));
   Device::PendingFree pf{p, {}};
   auto mark = [&](hipStream_t st) -> hipError_t {
@@ -1589,7 +1615,7 @@ int pbftv_host_free(pbftv_ctx* ctx, void* ptr) {
 
 int pbftv_dev_free(pbftv_ctx* ctx, int dev, void* ptr) {
   Device* d = dev_of(ctx, dev);
-  if (!d) return fail(PBFTV_EINVAL, "bad context or device index");
+  if (!d) return bad_dev();
   if (!ptr) return PBFTV_OK;
   std::lock_guard<std::mutex> lk(d->mu);
   HIP_TRY(hipSetDevice(d->id));
@@ -1684,7 +1710,7 @@ int pbftv_stream_wait(pbftv_ctx* ctx, int dev, void* stream) {
 
 int pbftv_stream_sync(pbftv_ctx* ctx, int dev) {
   Device* d = dev_of(ctx, dev);
-  if (!d) return fail(PBFTV_EINVAL, "bad context or device index");
+  if (!d) return bad_dev();
   HIP_TRY(hipSetDevice(d->id));
   HIP_TRY(hipStreamSynchronize(d->stream));
   return PBFTV_OK;
@@ -1702,51 +1728,41 @@ int pbftv_set_kernel_timing(pbftv_ctx* ctx, int enable) {
   return PBFTV_OK;
 }
 
-int pbftv_kernel_time_ms(pbftv_ctx* ctx, int dev, int kernel, double* out_ms, uint64_t* out_launches) {
-  Device* d = dev_of(ctx, dev);
-  if (!d || kernel < 0 || kernel >= Device::kKernels) return fail(PBFTV_EINVAL, "bad argument");
-  std::lock_guard<std::mutex> lk(d->mu);
-  HIP_TRY(hipSetDevice(d->id));
-  HIP_TRY(collect_times(*d));
-  if (out_ms) *out_ms = d->acc_ms[kernel];
-  if (out_launches) *out_launches = d->launches[kernel];
-  return PBFTV_OK;
-}
-
-// timing id PBFTV_K_ECDSA_DER (k_der_to_rs): a slot of its own (Device::der),
-// read here; pbftv_kernel_time_ms and its arrays stay as they were
-static hipError_t der_collect_times(Device& d);
-
-int pbftv_der_kernel_time_ms(pbftv_ctx* ctx, int dev, double* out_ms, uint64_t* out_launches) {
-  Device* d = dev_of(ctx, dev);
+// The three getters read slots [lo, hi) of the device's one timing table
+// (Device::timers), summed, after collecting what is pending; d null: a
+// refused argument.
+static int kernel_time(Device* d, int lo, int hi, double* out_ms, uint64_t* out_launches) {
   if (!d) return fail(PBFTV_EINVAL, "bad argument");
   std::lock_guard<std::mutex> lk(d->mu);
   HIP_TRY(hipSetDevice(d->id));
-  HIP_TRY(der_collect_times(*d));
-  if (out_ms) *out_ms = d->der.acc_ms;
-  if (out_launches) *out_launches = d->der.launches;
-  return PBFTV_OK;
-}
-
-// timing id PBFTV_K_ECDSA_SIGN (the sign stages): slots of its own (Device::sign)
-static hipError_t sign_collect_times(Device& d);
-
-int pbftv_sign_kernel_time_ms(pbftv_ctx* ctx, int dev, int stage, double* out_ms, uint64_t* out_launches) {
-  Device* d = dev_of(ctx, dev);
-  if (!d || stage < 0 || stage > Device::Sign::kStages) return fail(PBFTV_EINVAL, "bad argument");
-  std::lock_guard<std::mutex> lk(d->mu);
-  HIP_TRY(hipSetDevice(d->id));
-  HIP_TRY(sign_collect_times(*d));
+  HIP_TRY(collect_times(*d));
   double ms = 0;
   uint64_t launches = 0;
-  for (int k = 0; k < Device::Sign::kStages; ++k)
-    if (stage == 0 || stage == k + 1) {
-      ms += d->sign.acc_ms[k];
-      launches += d->sign.launches[k];
-    }
+  for (int k = lo; k < hi; ++k) {
+    ms += d->timers.ms(k);
+    launches += d->timers.launches(k);
+  }
   if (out_ms) *out_ms = ms;
   if (out_launches) *out_launches = launches;
   return PBFTV_OK;
+}
+
+// ids 0..5; the DER and sign ids have getters of their own
+int pbftv_kernel_time_ms(pbftv_ctx* ctx, int dev, int kernel, double* out_ms, uint64_t* out_launches) {
+  const bool ok = kernel >= 0 && kernel < Device::kKernels;
+  return kernel_time(ok ? dev_of(ctx, dev) : nullptr, kernel, kernel + 1, out_ms, out_launches);
+}
+
+int pbftv_der_kernel_time_ms(pbftv_ctx* ctx, int dev, double* out_ms, uint64_t* out_launches) {
+  return kernel_time(dev_of(ctx, dev), PBFTV_K_ECDSA_DER, PBFTV_K_ECDSA_DER + 1, out_ms, out_launches);
+}
+
+// stage 0: the sum of the four stages; 1..4: one of them
+int pbftv_sign_kernel_time_ms(pbftv_ctx* ctx, int dev, int stage, double* out_ms, uint64_t* out_launches) {
+  const bool ok = stage >= 0 && stage <= Device::kSignStages;
+  const int lo = PBFTV_K_ECDSA_SIGN + (stage ? stage - 1 : 0);
+  return kernel_time(ok ? dev_of(ctx, dev) : nullptr, lo, stage ? lo + 1 : lo + Device::kSignStages, out_ms,
+                     out_launches);
 }
 
 int pbftv_reset_kernel_times(pbftv_ctx* ctx) {
@@ -1755,18 +1771,7 @@ int pbftv_reset_kernel_times(pbftv_ctx* ctx) {
     std::lock_guard<std::mutex> lk(dp->mu);
     HIP_TRY(hipSetDevice(dp->id));
     HIP_TRY(collect_times(*dp));
-    for (int k = 0; k < Device::kKernels; ++k) {
-      dp->acc_ms[k] = 0;
-      dp->launches[k] = 0;
-    }
-    HIP_TRY(der_collect_times(*dp));
-    dp->der.acc_ms = 0;
-    dp->der.launches = 0;
-    HIP_TRY(sign_collect_times(*dp));
-    for (int k = 0; k < Device::Sign::kStages; ++k) {
-      dp->sign.acc_ms[k] = 0;
-      dp->sign.launches[k] = 0;
-    }
+    dp->timers.reset();
   }
   return PBFTV_OK;
 }
@@ -2001,6 +2006,19 @@ static int acquire_g_table(Device& d, int wg, std::shared_ptr<DevBuf>* out,
   return PBFTV_OK;
 }
 
+// The width-16 G table of the verify under unregistered keys and of the signer
+// (Device::vb_gtab), with the GPU's compute-unit count: taken from the per-GPU
+// cache at the first use (built if no context holds it), kept until the
+// context closes.  d.mu is held.
+static int ensure_vb_gtab(Device& d) {
+  if (d.vb_gtab) return PBFTV_OK;
+  auto t0 = std::chrono::steady_clock::now();
+  const int r = acquire_g_table(d, pbftv::kVarbaseGBits, &d.vb_gtab, t0);
+  if (r != PBFTV_OK) return r;
+  HIP_TRY(hipDeviceGetAttribute(&d.vb_cus, hipDeviceAttributeMultiprocessorCount, d.id));
+  return PBFTV_OK;
+}
+
 // One attempt at a device's tables: geometry from the HBM free now, then the G
 // table (shared per GPU and width) and the key tables (pbftv_register_keys).
 static int register_tables(Device& d, const std::vector<uint32_t>& le, uint32_t k, uint32_t* valid,
@@ -2188,15 +2206,13 @@ static int verify_on_device(Device& d, const uint8_t* d_hashes, const uint8_t* d
     HIP_TRY(fence_reader(d, st));
     return PBFTV_OK;
   }
-  if (!own) {
-    auto it = d.stream_scratch.find(st);
-    if (it != d.stream_scratch.end()) own = it->second.get();
-  }
+  own = own_scratch(d, st, own);
   VerifyScratch& sc = own ? *own : d.vs;
   note_busy(d, n);
   HIP_TRY(sc.rec.ensure(pbftv::ecdsa_record_bytes(n)));
   HIP_TRY(sc.prefix.ensure(pbftv::scalar_prefix_bytes(n)));
-  if (!own) HIP_TRY(scratch_acquire(d, st));
+  ScratchLease lease(d.scratch, st, !own);
+  HIP_TRY(lease.acquire());
   const bool sorted = pbftv::key_sort_wanted(n, d.nkeys);
   pbftv::KeyOrder ko{nullptr, nullptr, 0};
   if (sorted) {
@@ -2221,7 +2237,7 @@ static int verify_on_device(Device& d, const uint8_t* d_hashes, const uint8_t* d
                                     st);
   }));
   if (sorted) HIP_TRY(pbftv::launch_pack_bits(sc.okb.as<uint8_t>(), n, d_bitmap, st));
-  if (!own) HIP_TRY(scratch_release(d, st));
+  HIP_TRY(lease.release());
   return PBFTV_OK;
 }
 
@@ -2334,13 +2350,12 @@ static int verify_host_pipelined(Device& d, const uint8_t* H, const uint8_t* S, 
 
 int pbftv_ecdsa_p256_verify_batch_dev(pbftv_ctx* ctx, int dev, const uint8_t* d_hashes, const uint8_t* d_sig_rs,
                                       const uint32_t* d_key_idx, uint64_t n, uint8_t* d_bitmap, void* stream) {
-  if (!ctx || dev < 0 || dev >= (int)ctx->devs.size()) return fail(PBFTV_EINVAL, "bad context or device index");
+  DevEntry e;
+  if (const int rc = e.args(ctx, dev)) return rc;
   if (n && (!d_hashes || !d_sig_rs || !d_key_idx || !d_bitmap)) return fail(PBFTV_EINVAL, "null buffer");
   if (((uintptr_t)d_hashes | (uintptr_t)d_sig_rs) & 15u) return fail(PBFTV_EINVAL, "hashes/sigs must be 16-B aligned");
-  Device& d = *ctx->devs[dev];
-  std::lock_guard<std::mutex> lk(d.mu);
-  HIP_TRY(hipSetDevice(d.id));
-  return verify_on_device(d, d_hashes, d_sig_rs, d_key_idx, n, d_bitmap, pick_stream(d, stream));
+  if (const int rc = e.enter(stream)) return rc;
+  return verify_on_device(*e.dev, d_hashes, d_sig_rs, d_key_idx, n, d_bitmap, e.st);
 }
 
 // ---- verify under keys that were never registered (varbase.h) ----
@@ -2360,15 +2375,8 @@ uint32_t pbftv_key_bytes(int key_format) { return pbftv::varbase_key_bytes(key_f
 static int varbase_on_device(Device& d, const uint8_t* d_hashes, const uint8_t* d_sigs, const uint8_t* d_keys,
                              int key_format, uint64_t n, uint8_t* d_bitmap, hipStream_t st) {
   if (n == 0) return PBFTV_OK;
-  if (!d.vb_gtab) {  // first use: the G table from the per-GPU cache (built if no context holds it)
-    auto t0 = std::chrono::steady_clock::now();
-    const int r = acquire_g_table(d, pbftv::kVarbaseGBits, &d.vb_gtab, t0);
-    if (r != PBFTV_OK) return r;
-    HIP_TRY(hipDeviceGetAttribute(&d.vb_cus, hipDeviceAttributeMultiprocessorCount, d.id));
-  }
-  VerifyScratch* own = nullptr;
-  auto it = d.stream_scratch.find(st);
-  if (it != d.stream_scratch.end()) own = it->second.get();
+  if (const int r = ensure_vb_gtab(d)) return r;
+  VerifyScratch* const own = own_scratch(d, st);
   VerifyScratch& sc = own ? *own : d.vs;
   note_busy(d, n, 19.0);  // (~19 ns per signature at 1M)
   const uint64_t lanes = std::min<uint64_t>(pbftv::varbase_lanes(d.vb_cus), (n + 255) / 256 * 256);
@@ -2376,7 +2384,8 @@ static int varbase_on_device(Device& d, const uint8_t* d_hashes, const uint8_t* 
   HIP_TRY(sc.prefix.ensure(pbftv::scalar_prefix_bytes(n)));
   HIP_TRY(sc.vb_aux.ensure(pbftv::varbase_aux_bytes(n)));
   HIP_TRY(sc.vb_tab.ensure(pbftv::varbase_table_bytes(lanes)));
-  if (!own) HIP_TRY(scratch_acquire(d, st));
+  ScratchLease lease(d.scratch, st, !own);
+  HIP_TRY(lease.acquire());
   HIP_TRY(pbftv::launch_varbase_keys(d_keys, key_format, n, sc.vb_aux.p, st));
   HIP_TRY(timed(d, PBFTV_K_ECDSA_SCALARS, st, [&] {
     return pbftv::launch_ecdsa_scalars(d_hashes, d_sigs, pbftv::varbase_index(sc.vb_aux.p, n), n,
@@ -2387,24 +2396,23 @@ static int varbase_on_device(Device& d, const uint8_t* d_hashes, const uint8_t* 
     return pbftv::launch_varbase(sc.rec.p, sc.vb_aux.p, n, d.vb_gtab->as<uint32_t>(), sc.vb_tab.p, lanes, d_bitmap,
                                  st);
   }));
-  if (!own) HIP_TRY(scratch_release(d, st));
+  HIP_TRY(lease.release());
   return PBFTV_OK;
 }
 
 int pbftv_ecdsa_p256_verify_wirekey_batch_dev(pbftv_ctx* ctx, int dev, const uint8_t* d_hashes,
                                               const uint8_t* d_sig_rs, const uint8_t* d_keys, int key_format,
                                               uint64_t n, uint8_t* d_bitmap, void* stream) {
-  if (!ctx || dev < 0 || dev >= (int)ctx->devs.size()) return fail(PBFTV_EINVAL, "bad context or device index");
+  DevEntry e;
+  if (const int rc = e.args(ctx, dev)) return rc;
   if (!pbftv_key_bytes(key_format)) return fail(PBFTV_EINVAL, "unknown key format");
-  if (n >> 32) return fail(PBFTV_EINVAL, "n must be below 2^32");
+  if (const int rc = n_below_2_32(n)) return rc;
   if (n == 0) return PBFTV_OK;
   if (!d_hashes || !d_sig_rs || !d_keys || !d_bitmap) return fail(PBFTV_EINVAL, "null buffer");
   if (((uintptr_t)d_hashes | (uintptr_t)d_sig_rs | (uintptr_t)d_keys) & 15u)
     return fail(PBFTV_EINVAL, "hashes/sigs/keys must be 16-B aligned");
-  Device& d = *ctx->devs[dev];
-  std::lock_guard<std::mutex> lk(d.mu);
-  HIP_TRY(hipSetDevice(d.id));
-  return varbase_on_device(d, d_hashes, d_sig_rs, d_keys, key_format, n, d_bitmap, pick_stream(d, stream));
+  if (const int rc = e.enter(stream)) return rc;
+  return varbase_on_device(*e.dev, d_hashes, d_sig_rs, d_keys, key_format, n, d_bitmap, e.st);
 }
 
 int pbftv_ecdsa_p256_verify_pubkey_batch_dev(pbftv_ctx* ctx, int dev, const uint8_t* d_hashes,
@@ -2427,22 +2435,18 @@ int pbftv_ecdsa_p256_verify_wirekey_batch(pbftv_ctx* ctx, const uint8_t* hashes,
   if (n == 0) return PBFTV_OK;
   if (!hashes || !sig_rs || !keys || !out_bitmap) return fail(PBFTV_EINVAL, "null buffer");
   return run_sharded(ctx, n, [&](Device& d, Shard s) -> int {
-    std::lock_guard<std::mutex> lk(d.mu);
-    HIP_TRY(hipSetDevice(d.id));
-    const uint64_t m = s.hi - s.lo;
-    HIP_TRY(d.hashes.ensure(32 * m + 64));
-    HIP_TRY(d.sigs.ensure(64 * m + 64));
-    HIP_TRY(d.vb_pub.ensure(stride * m + 64));
-    HIP_TRY(d.bitmap.ensure((m + 7) / 8 + 8));
-    HIP_TRY(hipMemcpyAsync(d.hashes.p, hashes + 32 * s.lo, 32 * m, hipMemcpyHostToDevice, d.stream));
-    HIP_TRY(hipMemcpyAsync(d.sigs.p, sig_rs + 64 * s.lo, 64 * m, hipMemcpyHostToDevice, d.stream));
-    HIP_TRY(hipMemcpyAsync(d.vb_pub.p, keys + stride * s.lo, stride * m, hipMemcpyHostToDevice, d.stream));
-    const int rc = varbase_on_device(d, d.hashes.as<uint8_t>(), d.sigs.as<uint8_t>(), d.vb_pub.as<uint8_t>(),
-                                     key_format, m, d.bitmap.as<uint8_t>(), d.stream);
-    if (rc != PBFTV_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(out_bitmap + s.lo / 8, d.bitmap.p, (m + 7) / 8, hipMemcpyDeviceToHost, d.stream));
-    HIP_TRY(hipStreamSynchronize(d.stream));
-    return PBFTV_OK;
+    return shard_round_trip(d, [&]() -> int {
+      const uint64_t m = s.hi - s.lo;
+      HIP_TRY(copy_in(d, d.hashes, hashes + 32 * s.lo, 32 * m, 64));
+      HIP_TRY(copy_in(d, d.sigs, sig_rs + 64 * s.lo, 64 * m, 64));
+      HIP_TRY(copy_in(d, d.vb_pub, keys + stride * s.lo, stride * m, 64));
+      HIP_TRY(d.bitmap.ensure((m + 7) / 8 + 8));
+      const int rc = varbase_on_device(d, d.hashes.as<uint8_t>(), d.sigs.as<uint8_t>(), d.vb_pub.as<uint8_t>(),
+                                       key_format, m, d.bitmap.as<uint8_t>(), d.stream);
+      if (rc != PBFTV_OK) return rc;
+      HIP_TRY(hipMemcpyAsync(out_bitmap + s.lo / 8, d.bitmap.p, (m + 7) / 8, hipMemcpyDeviceToHost, d.stream));
+      return PBFTV_OK;
+    });
   });
 }
 
@@ -2720,55 +2724,29 @@ int pbftv_ecdsa_p256_verify_batch(pbftv_ctx* ctx, const uint8_t* hashes, const u
 // uses no device scratch.
 static int der_on_device(Device& d, const uint8_t* d_data, const uint64_t* d_off, const uint32_t* d_len, uint64_t n,
                          uint8_t* d_out_rs, uint8_t* d_parsed, hipStream_t st) {
-  if (!d.timing || !*d.timing) {
-    HIP_TRY(pbftv::launch_der_to_rs(d_data, d_off, d_len, n, d_out_rs, d_parsed, st));
-    return PBFTV_OK;
-  }
-  hipEvent_t a, b;  // (as timed(): events around the launch, collected by pbftv_der_kernel_time_ms)
-  HIP_TRY(hipEventCreate(&a));
-  HIP_TRY(hipEventCreate(&b));
-  (void)hipEventRecord(a, st);
-  const hipError_t e = pbftv::launch_der_to_rs(d_data, d_off, d_len, n, d_out_rs, d_parsed, st);
-  (void)hipEventRecord(b, st);
-  d.der.pending.push_back({a, b});
-  HIP_TRY(e);
+  HIP_TRY(timed(d, PBFTV_K_ECDSA_DER, st, [&] {
+    return pbftv::launch_der_to_rs(d_data, d_off, d_len, n, d_out_rs, d_parsed, st);
+  }));
   return PBFTV_OK;
-}
-
-// the DER slot's pending events into its sums (collect_times for id 6)
-static hipError_t der_collect_times(Device& d) {
-  for (auto& pr : d.der.pending) {
-    HIP_TRY_E(hipEventSynchronize(pr.second));
-    float ms = 0;
-    HIP_TRY_E(hipEventElapsedTime(&ms, pr.first, pr.second));
-    d.der.acc_ms += ms;
-    d.der.launches += 1;
-    (void)hipEventDestroy(pr.first);
-    (void)hipEventDestroy(pr.second);
-  }
-  d.der.pending.clear();
-  return hipSuccess;
 }
 
 int pbftv_ecdsa_der_to_rs_batch_dev(pbftv_ctx* ctx, int dev, const uint8_t* d_data, const uint64_t* d_offsets,
                                     const uint32_t* d_lengths, uint64_t n, uint8_t* d_out_rs,
                                     uint8_t* d_parsed_bitmap, void* stream) {
-  if (!ctx || dev < 0 || dev >= (int)ctx->devs.size()) return fail(PBFTV_EINVAL, "bad context or device index");
-  if (n >> 32) return fail(PBFTV_EINVAL, "n must be below 2^32");
+  DevEntry e;
+  if (const int rc = e.args(ctx, dev, n)) return rc;
   if (n == 0) return PBFTV_OK;
   // (d_data may be null when every length is zero: the lengths live on the device)
   if (!d_offsets || !d_lengths || !d_out_rs) return fail(PBFTV_EINVAL, "null buffer");
   if ((uintptr_t)d_out_rs & 15u) return fail(PBFTV_EINVAL, "out_rs must be 16-B aligned");
   if (((uintptr_t)d_offsets & 7u) || ((uintptr_t)d_lengths & 3u))
     return fail(PBFTV_EINVAL, "offsets / lengths must be 8-B / 4-B aligned");
-  Device& d = *ctx->devs[dev];
-  std::lock_guard<std::mutex> lk(d.mu);
-  HIP_TRY(hipSetDevice(d.id));
-  hipStream_t st = pick_stream(d, stream);
+  if (const int rc = e.enter(stream)) return rc;
+  Device& d = *e.dev;
   note_busy(d, n, 0.05);
-  const int rc = der_on_device(d, d_data, d_offsets, d_lengths, n, d_out_rs, d_parsed_bitmap, st);
+  const int rc = der_on_device(d, d_data, d_offsets, d_lengths, n, d_out_rs, d_parsed_bitmap, e.st);
   if (rc != PBFTV_OK) return rc;
-  HIP_TRY(fence_reader(d, st));
+  HIP_TRY(fence_reader(d, e.st));
   return PBFTV_OK;
 }
 
@@ -2785,48 +2763,47 @@ static int verify_der_on_device(Device& d, const uint8_t* d_hashes, const uint8_
   if (!d_keys && !d.have_keys) return fail(PBFTV_ENOKEYS, "pbftv_register_keys has not been called");
   HIP_TRY(d.der.rs.ensure(64 * n));
   uint8_t* rs = d.der.rs.as<uint8_t>();
-  HIP_TRY(scratch_acquire(d, st));
+  ScratchLease lease(d.scratch, st);
+  HIP_TRY(lease.acquire());
   int rc = der_on_device(d, d_der, d_off, d_len, n, rs, nullptr, st);
-  HIP_TRY(scratch_release(d, st));
   if (rc != PBFTV_OK) return rc;
+  HIP_TRY(lease.release());
   rc = d_keys ? varbase_on_device(d, d_hashes, rs, d_keys, key_format, n, d_bitmap, st)
               : verify_on_device(d, d_hashes, rs, d_key_idx, n, d_bitmap, st);
   // the verify read rs, whichever path it took and whichever scratch it used
-  // itself: the next user of rs on another stream waits for this point
-  if (rc == PBFTV_OK) HIP_TRY(scratch_release(d, st));
+  // itself: the next user of rs on another stream waits for this point (also
+  // after a verify that failed part-way: what it did enqueue reads rs)
+  const hipError_t e = lease.release();
+  if (rc == PBFTV_OK) HIP_TRY(e);
   return rc;
 }
 
 int pbftv_ecdsa_p256_verify_der_batch_dev(pbftv_ctx* ctx, int dev, const uint8_t* d_hashes, const uint8_t* d_der,
                                           const uint64_t* d_der_off, const uint32_t* d_der_len,
                                           const uint32_t* d_key_idx, uint64_t n, uint8_t* d_bitmap, void* stream) {
-  if (!ctx || dev < 0 || dev >= (int)ctx->devs.size()) return fail(PBFTV_EINVAL, "bad context or device index");
-  if (n >> 32) return fail(PBFTV_EINVAL, "n must be below 2^32");
+  DevEntry e;
+  if (const int rc = e.args(ctx, dev, n)) return rc;
   if (n == 0) return PBFTV_OK;
   if (!d_hashes || !d_der_off || !d_der_len || !d_key_idx || !d_bitmap) return fail(PBFTV_EINVAL, "null buffer");
   if ((uintptr_t)d_hashes & 15u) return fail(PBFTV_EINVAL, "hashes must be 16-B aligned");
-  Device& d = *ctx->devs[dev];
-  std::lock_guard<std::mutex> lk(d.mu);
-  HIP_TRY(hipSetDevice(d.id));
-  return verify_der_on_device(d, d_hashes, d_der, d_der_off, d_der_len, d_key_idx, nullptr, 0, n, d_bitmap,
-                              pick_stream(d, stream));
+  if (const int rc = e.enter(stream)) return rc;
+  return verify_der_on_device(*e.dev, d_hashes, d_der, d_der_off, d_der_len, d_key_idx, nullptr, 0, n, d_bitmap, e.st);
 }
 
 int pbftv_ecdsa_p256_verify_wirekey_der_batch_dev(pbftv_ctx* ctx, int dev, const uint8_t* d_hashes,
                                                   const uint8_t* d_der, const uint64_t* d_der_off,
                                                   const uint32_t* d_der_len, const uint8_t* d_keys, int key_format,
                                                   uint64_t n, uint8_t* d_bitmap, void* stream) {
-  if (!ctx || dev < 0 || dev >= (int)ctx->devs.size()) return fail(PBFTV_EINVAL, "bad context or device index");
+  DevEntry e;
+  if (const int rc = e.args(ctx, dev)) return rc;
   if (!pbftv_key_bytes(key_format)) return fail(PBFTV_EINVAL, "unknown key format");
-  if (n >> 32) return fail(PBFTV_EINVAL, "n must be below 2^32");
+  if (const int rc = n_below_2_32(n)) return rc;
   if (n == 0) return PBFTV_OK;
   if (!d_hashes || !d_der_off || !d_der_len || !d_keys || !d_bitmap) return fail(PBFTV_EINVAL, "null buffer");
   if (((uintptr_t)d_hashes | (uintptr_t)d_keys) & 15u) return fail(PBFTV_EINVAL, "hashes/keys must be 16-B aligned");
-  Device& d = *ctx->devs[dev];
-  std::lock_guard<std::mutex> lk(d.mu);
-  HIP_TRY(hipSetDevice(d.id));
-  return verify_der_on_device(d, d_hashes, d_der, d_der_off, d_der_len, nullptr, d_keys, key_format, n, d_bitmap,
-                              pick_stream(d, stream));
+  if (const int rc = e.enter(stream)) return rc;
+  return verify_der_on_device(*e.dev, d_hashes, d_der, d_der_off, d_der_len, nullptr, d_keys, key_format, n, d_bitmap,
+                              e.st);
 }
 
 // A shard's DER column on the device (d.mu held, on d.stream): the span its
@@ -2835,22 +2812,13 @@ int pbftv_ecdsa_p256_verify_wirekey_der_batch_dev(pbftv_ctx* ctx, int dev, const
 // holds the rebased offsets until the caller has synchronised.
 static int der_column_in(Device& d, const uint8_t* der, const uint64_t* off, const uint32_t* len, uint64_t lo,
                          uint64_t m, std::vector<uint64_t>& keep) {
-  uint64_t a = UINT64_MAX, b = 0;
-  for (uint64_t i = lo; i < lo + m; ++i)
-    if (len[i]) {
-      a = std::min(a, off[i]);
-      b = std::max(b, off[i] + std::min<uint32_t>(len[i], pbftv::kDerMaxBytes));
-    }
-  if (a > b) a = b = 0;
+  const StrSpan sp = str_span(off, len, lo, lo + m, pbftv::kDerMaxBytes, keep);
+  const uint64_t a = sp.a, b = sp.b;
   if (b > a && der == nullptr) return fail(PBFTV_EINVAL, "DER column: nonzero lengths with a null data pointer");
-  keep.resize(m);
-  for (uint64_t i = 0; i < m; ++i) keep[i] = len[lo + i] ? off[lo + i] - a : 0;
   HIP_TRY(d.data.ensure(b - a + 64));
-  HIP_TRY(d.offsets.ensure(8 * m + 8));
-  HIP_TRY(d.lengths.ensure(4 * m + 4));
   if (b > a) HIP_TRY(hipMemcpyAsync(d.data.p, der + a, b - a, hipMemcpyHostToDevice, d.stream));
-  HIP_TRY(hipMemcpyAsync(d.offsets.p, keep.data(), 8 * m, hipMemcpyHostToDevice, d.stream));
-  HIP_TRY(hipMemcpyAsync(d.lengths.p, len + lo, 4 * m, hipMemcpyHostToDevice, d.stream));
+  HIP_TRY(copy_in(d, d.offsets, keep.data(), 8 * m, 8));
+  HIP_TRY(copy_in(d, d.lengths, len + lo, 4 * m, 4));
   return PBFTV_OK;
 }
 
@@ -2863,33 +2831,23 @@ static int verify_der_host_sharded(pbftv_ctx* ctx, const uint8_t* hashes, const 
                                    int key_format, uint64_t n, uint8_t* out_bitmap) {
   const uint64_t stride = keys ? pbftv_key_bytes(key_format) : 0;
   return run_sharded(ctx, n, [&](Device& d, Shard s) -> int {
-    std::lock_guard<std::mutex> lk(d.mu);
-    HIP_TRY(hipSetDevice(d.id));
     const uint64_t m = s.hi - s.lo;
     std::vector<uint64_t> keep;  // (source of an asynchronous copy: alive until d.stream has been synchronised)
-    const int rc = [&]() -> int {
-    int rc = der_column_in(d, der, der_off, der_len, s.lo, m, keep);
-    if (rc != PBFTV_OK) return rc;
-    HIP_TRY(d.hashes.ensure(32 * m + 64));
-    HIP_TRY(d.bitmap.ensure((m + 7) / 8 + 8));
-    HIP_TRY(hipMemcpyAsync(d.hashes.p, hashes + 32 * s.lo, 32 * m, hipMemcpyHostToDevice, d.stream));
-    if (keys) {
-      HIP_TRY(d.vb_pub.ensure(stride * m + 64));
-      HIP_TRY(hipMemcpyAsync(d.vb_pub.p, keys + stride * s.lo, stride * m, hipMemcpyHostToDevice, d.stream));
-    } else {
-      HIP_TRY(d.key_idx.ensure(4 * m + 64));
-      HIP_TRY(hipMemcpyAsync(d.key_idx.p, key_idx + s.lo, 4 * m, hipMemcpyHostToDevice, d.stream));
-    }
-    rc = verify_der_on_device(d, d.hashes.as<uint8_t>(), d.data.as<uint8_t>(), d.offsets.as<uint64_t>(),
-                              d.lengths.as<uint32_t>(), keys ? nullptr : d.key_idx.as<uint32_t>(),
-                              keys ? d.vb_pub.as<uint8_t>() : nullptr, key_format, m, d.bitmap.as<uint8_t>(), d.stream);
-    if (rc != PBFTV_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(out_bitmap + s.lo / 8, d.bitmap.p, (m + 7) / 8, hipMemcpyDeviceToHost, d.stream));
-    HIP_TRY(hipStreamSynchronize(d.stream));
-    return PBFTV_OK;
-    }();
-    if (rc != PBFTV_OK) (void)hipStreamSynchronize(d.stream);  // (fail() has kept the first error's message)
-    return rc;
+    return shard_round_trip(d, [&]() -> int {
+      int rc = der_column_in(d, der, der_off, der_len, s.lo, m, keep);
+      if (rc != PBFTV_OK) return rc;
+      HIP_TRY(d.bitmap.ensure((m + 7) / 8 + 8));
+      HIP_TRY(copy_in(d, d.hashes, hashes + 32 * s.lo, 32 * m, 64));
+      if (keys) HIP_TRY(copy_in(d, d.vb_pub, keys + stride * s.lo, stride * m, 64));
+      else HIP_TRY(copy_in(d, d.key_idx, key_idx + s.lo, 4 * m, 64));
+      rc = verify_der_on_device(d, d.hashes.as<uint8_t>(), d.data.as<uint8_t>(), d.offsets.as<uint64_t>(),
+                                d.lengths.as<uint32_t>(), keys ? nullptr : d.key_idx.as<uint32_t>(),
+                                keys ? d.vb_pub.as<uint8_t>() : nullptr, key_format, m, d.bitmap.as<uint8_t>(),
+                                d.stream);
+      if (rc != PBFTV_OK) return rc;
+      HIP_TRY(hipMemcpyAsync(out_bitmap + s.lo / 8, d.bitmap.p, (m + 7) / 8, hipMemcpyDeviceToHost, d.stream));
+      return PBFTV_OK;
+    });
   });
 }
 
@@ -2925,40 +2883,6 @@ int pbftv_ecdsa_p256_verify_wirekey_der_batch(pbftv_ctx* ctx, const uint8_t* has
 }
 
 // ---- signing: RFC 6979 ECDSA-P256 in batches (sign.h, p256_sign.hip) ----
-// one timed launch of a sign stage (as timed(): events around it, collected by
-// pbftv_sign_kernel_time_ms)
-static int sign_timed(Device& d, int slot, hipStream_t st, const std::function<hipError_t()>& launch) {
-  if (!d.timing || !*d.timing) {
-    HIP_TRY(launch());
-    return PBFTV_OK;
-  }
-  hipEvent_t a, b;
-  HIP_TRY(hipEventCreate(&a));
-  HIP_TRY(hipEventCreate(&b));
-  (void)hipEventRecord(a, st);
-  const hipError_t e = launch();
-  (void)hipEventRecord(b, st);
-  d.sign.pending[slot].push_back({a, b});
-  HIP_TRY(e);
-  return PBFTV_OK;
-}
-
-static hipError_t sign_collect_times(Device& d) {
-  for (int k = 0; k < Device::Sign::kStages; ++k) {
-    for (auto& pr : d.sign.pending[k]) {
-      HIP_TRY_E(hipEventSynchronize(pr.second));
-      float ms = 0;
-      HIP_TRY_E(hipEventElapsedTime(&ms, pr.first, pr.second));
-      d.sign.acc_ms[k] += ms;
-      d.sign.launches[k] += 1;
-      (void)hipEventDestroy(pr.first);
-      (void)hipEventDestroy(pr.second);
-    }
-    d.sign.pending[k].clear();
-  }
-  return hipSuccess;
-}
-
 int pbftv_register_signing_keys(pbftv_ctx* ctx, const uint8_t* priv, uint32_t k, uint8_t* out_valid) {
   if (!ctx || (k && !priv)) return fail(PBFTV_EINVAL, "null argument");
   // host staging: the keys' words, then their validity words; zeroed below
@@ -3019,23 +2943,18 @@ static int sign_on_device(Device& d, const uint8_t* d_hashes, const uint32_t* d_
                           uint8_t* d_out_rs, uint8_t* d_okbits, hipStream_t st) {
   if (n == 0) return PBFTV_OK;
   if (!d.sign.have) return fail(PBFTV_ENOSIGNKEYS, "pbftv_register_signing_keys has not been called");
-  if (!d.vb_gtab) {
-    auto t0 = std::chrono::steady_clock::now();
-    const int r = acquire_g_table(d, pbftv::kVarbaseGBits, &d.vb_gtab, t0);
-    if (r != PBFTV_OK) return r;
-    HIP_TRY(hipDeviceGetAttribute(&d.vb_cus, hipDeviceAttributeMultiprocessorCount, d.id));
-  }
+  if (const int r = ensure_vb_gtab(d)) return r;
   HIP_TRY(d.sign.rec.ensure(pbftv::sign_record_bytes(n)));
   note_busy(d, n, 30.0);
   const uint32_t* keys = d.sign.keys.as<uint32_t>();
   const pbftv::SignArgs a{d_hashes, d_skey_idx, keys, keys + 8 * (size_t)d.sign.nkeys, d.sign.nkeys, n,
                           d.vb_gtab->as<uint32_t>(), d.sign.rec.p, d_out_rs, d_okbits};
-  HIP_TRY(scratch_acquire(d, st));
-  int rc = PBFTV_OK;
-  for (int stage = 0; stage < pbftv::kSignStages && rc == PBFTV_OK; ++stage)
-    rc = sign_timed(d, stage, st, [&] { return pbftv::launch_sign_stage(stage, a, st); });
-  HIP_TRY(scratch_release(d, st));
-  return rc;
+  ScratchLease lease(d.scratch, st);
+  HIP_TRY(lease.acquire());
+  for (int stage = 0; stage < pbftv::kSignStages; ++stage)
+    HIP_TRY(timed(d, PBFTV_K_ECDSA_SIGN + stage, st, [&] { return pbftv::launch_sign_stage(stage, a, st); }));
+  HIP_TRY(lease.release());
+  return PBFTV_OK;
 }
 
 // ... and with the signatures written as DER: the batch signs into the
@@ -3046,46 +2965,64 @@ static int sign_der_on_device(Device& d, const uint8_t* d_hashes, const uint32_t
   if (!d.sign.have) return fail(PBFTV_ENOSIGNKEYS, "pbftv_register_signing_keys has not been called");
   HIP_TRY(d.sign.rs.ensure(64 * n));
   HIP_TRY(d.sign.okb.ensure((n + 7) / 8 + 8));
-  HIP_TRY(scratch_acquire(d, st));  // (rs and okb: held until the writer has read them)
-  int rc = sign_on_device(d, d_hashes, d_skey_idx, n, d.sign.rs.as<uint8_t>(), d.sign.okb.as<uint8_t>(), st);
-  if (rc == PBFTV_OK)
-    rc = sign_timed(d, 3, st, [&] {
-      return pbftv::launch_sign_der(d.sign.rs.as<uint8_t>(), d.sign.okb.as<uint8_t>(), n, d_out_der, d_out_len, st);
-    });
-  HIP_TRY(scratch_release(d, st));
-  return rc;
-}
-
-static int sign_dev_args(pbftv_ctx* ctx, int dev, uint64_t n) {
-  if (!ctx || dev < 0 || dev >= (int)ctx->devs.size()) return fail(PBFTV_EINVAL, "bad context or device index");
-  if (n >> 32) return fail(PBFTV_EINVAL, "n must be below 2^32");
+  ScratchLease lease(d.scratch, st);  // (rs and okb: held until the writer has read them)
+  HIP_TRY(lease.acquire());
+  const int rc = sign_on_device(d, d_hashes, d_skey_idx, n, d.sign.rs.as<uint8_t>(), d.sign.okb.as<uint8_t>(), st);
+  if (rc != PBFTV_OK) return rc;
+  HIP_TRY(timed(d, PBFTV_K_ECDSA_SIGN + pbftv::kSignStages, st, [&] {
+    return pbftv::launch_sign_der(d.sign.rs.as<uint8_t>(), d.sign.okb.as<uint8_t>(), n, d_out_der, d_out_len, st);
+  }));
+  HIP_TRY(lease.release());
   return PBFTV_OK;
 }
 
 int pbftv_ecdsa_p256_sign_batch_dev(pbftv_ctx* ctx, int dev, const uint8_t* d_hashes, const uint32_t* d_skey_idx,
                                     uint64_t n, uint8_t* d_out_sig_rs, uint8_t* d_out_ok_bitmap, void* stream) {
-  if (const int rc = sign_dev_args(ctx, dev, n)) return rc;
+  DevEntry e;
+  if (const int rc = e.args(ctx, dev, n)) return rc;
   if (n == 0) return PBFTV_OK;
   if (!d_hashes || !d_skey_idx || !d_out_sig_rs) return fail(PBFTV_EINVAL, "null buffer");
   if (((uintptr_t)d_hashes | (uintptr_t)d_out_sig_rs) & 15u)
     return fail(PBFTV_EINVAL, "hashes/signatures must be 16-B aligned");
-  Device& d = *ctx->devs[dev];
-  std::lock_guard<std::mutex> lk(d.mu);
-  HIP_TRY(hipSetDevice(d.id));
-  return sign_on_device(d, d_hashes, d_skey_idx, n, d_out_sig_rs, d_out_ok_bitmap, pick_stream(d, stream));
+  if (const int rc = e.enter(stream)) return rc;
+  return sign_on_device(*e.dev, d_hashes, d_skey_idx, n, d_out_sig_rs, d_out_ok_bitmap, e.st);
 }
 
 int pbftv_ecdsa_p256_sign_der_batch_dev(pbftv_ctx* ctx, int dev, const uint8_t* d_hashes, const uint32_t* d_skey_idx,
                                         uint64_t n, uint8_t* d_out_der, uint32_t* d_out_der_len, void* stream) {
-  if (const int rc = sign_dev_args(ctx, dev, n)) return rc;
+  DevEntry e;
+  if (const int rc = e.args(ctx, dev, n)) return rc;
   if (n == 0) return PBFTV_OK;
   if (!d_hashes || !d_skey_idx || !d_out_der || !d_out_der_len) return fail(PBFTV_EINVAL, "null buffer");
   if (((uintptr_t)d_hashes | (uintptr_t)d_out_der) & 15u)
     return fail(PBFTV_EINVAL, "hashes/DER slots must be 16-B aligned");
-  Device& d = *ctx->devs[dev];
-  std::lock_guard<std::mutex> lk(d.mu);
-  HIP_TRY(hipSetDevice(d.id));
-  return sign_der_on_device(d, d_hashes, d_skey_idx, n, d_out_der, d_out_der_len, pick_stream(d, stream));
+  if (const int rc = e.enter(stream)) return rc;
+  return sign_der_on_device(*e.dev, d_hashes, d_skey_idx, n, d_out_der, d_out_der_len, e.st);
+}
+
+// Shard [lo, lo + m) of a host form on d.stream (d.mu held): sign the m
+// digests on the device, then queue the copies of the signatures straight into
+// the caller's whole-batch buffers -- out_rs given: r||s rows and, if wanted,
+// ok bits; else DER slots and lengths.  The caller synchronises d.stream.
+static int sign_and_copy_out(Device& d, const uint8_t* d_hashes, const uint32_t* d_skey_idx, uint64_t lo, uint64_t m,
+                             uint8_t* out_rs, uint8_t* out_ok, uint8_t* out_der, uint32_t* out_der_len) {
+  if (out_rs) {
+    HIP_TRY(d.sigs.ensure(64 * m + 64));
+    HIP_TRY(d.bitmap.ensure((m + 7) / 8 + 8));
+    const int r = sign_on_device(d, d_hashes, d_skey_idx, m, d.sigs.as<uint8_t>(), d.bitmap.as<uint8_t>(), d.stream);
+    if (r != PBFTV_OK) return r;
+    HIP_TRY(hipMemcpyAsync(out_rs + 64 * lo, d.sigs.p, 64 * m, hipMemcpyDeviceToHost, d.stream));
+    if (out_ok) HIP_TRY(hipMemcpyAsync(out_ok + lo / 8, d.bitmap.p, (m + 7) / 8, hipMemcpyDeviceToHost, d.stream));
+    return PBFTV_OK;
+  }
+  HIP_TRY(d.sign.der.ensure(72 * m + 64));
+  HIP_TRY(d.sign.der_len.ensure(4 * m + 64));
+  const int r = sign_der_on_device(d, d_hashes, d_skey_idx, m, d.sign.der.as<uint8_t>(), d.sign.der_len.as<uint32_t>(),
+                                   d.stream);
+  if (r != PBFTV_OK) return r;
+  HIP_TRY(hipMemcpyAsync(out_der + 72 * lo, d.sign.der.p, 72 * m, hipMemcpyDeviceToHost, d.stream));
+  HIP_TRY(hipMemcpyAsync(out_der_len + lo, d.sign.der_len.p, 4 * m, hipMemcpyDeviceToHost, d.stream));
+  return PBFTV_OK;
 }
 
 // Host forms: contiguous shards over the context's devices; each copies its
@@ -3099,37 +3036,13 @@ static int sign_host(pbftv_ctx* ctx, const uint8_t* hashes, const uint32_t* skey
   if (!hashes || !skey_idx || !(out_rs || (out_der && out_der_len))) return fail(PBFTV_EINVAL, "null buffer");
   if (!sign_keys_ready(ctx)) return fail(PBFTV_ENOSIGNKEYS, "pbftv_register_signing_keys has not been called");
   return run_sharded(ctx, n, [&](Device& d, Shard s) -> int {
-    std::lock_guard<std::mutex> lk(d.mu);
-    HIP_TRY(hipSetDevice(d.id));
-    const uint64_t m = s.hi - s.lo;
-    const int rc = [&]() -> int {
-      HIP_TRY(d.hashes.ensure(32 * m + 64));
-      HIP_TRY(d.key_idx.ensure(4 * m + 64));
-      HIP_TRY(hipMemcpyAsync(d.hashes.p, hashes + 32 * s.lo, 32 * m, hipMemcpyHostToDevice, d.stream));
-      HIP_TRY(hipMemcpyAsync(d.key_idx.p, skey_idx + s.lo, 4 * m, hipMemcpyHostToDevice, d.stream));
-      if (out_rs) {
-        HIP_TRY(d.sigs.ensure(64 * m + 64));
-        HIP_TRY(d.bitmap.ensure((m + 7) / 8 + 8));
-        const int r = sign_on_device(d, d.hashes.as<uint8_t>(), d.key_idx.as<uint32_t>(), m, d.sigs.as<uint8_t>(),
-                                     d.bitmap.as<uint8_t>(), d.stream);
-        if (r != PBFTV_OK) return r;
-        HIP_TRY(hipMemcpyAsync(out_rs + 64 * s.lo, d.sigs.p, 64 * m, hipMemcpyDeviceToHost, d.stream));
-        if (out_ok)
-          HIP_TRY(hipMemcpyAsync(out_ok + s.lo / 8, d.bitmap.p, (m + 7) / 8, hipMemcpyDeviceToHost, d.stream));
-      } else {
-        HIP_TRY(d.sign.der.ensure(72 * m + 64));
-        HIP_TRY(d.sign.der_len.ensure(4 * m + 64));
-        const int r = sign_der_on_device(d, d.hashes.as<uint8_t>(), d.key_idx.as<uint32_t>(), m,
-                                         d.sign.der.as<uint8_t>(), d.sign.der_len.as<uint32_t>(), d.stream);
-        if (r != PBFTV_OK) return r;
-        HIP_TRY(hipMemcpyAsync(out_der + 72 * s.lo, d.sign.der.p, 72 * m, hipMemcpyDeviceToHost, d.stream));
-        HIP_TRY(hipMemcpyAsync(out_der_len + s.lo, d.sign.der_len.p, 4 * m, hipMemcpyDeviceToHost, d.stream));
-      }
-      HIP_TRY(hipStreamSynchronize(d.stream));
-      return PBFTV_OK;
-    }();
-    if (rc != PBFTV_OK) (void)hipStreamSynchronize(d.stream);  // (fail() has kept the first error's message)
-    return rc;
+    return shard_round_trip(d, [&]() -> int {
+      const uint64_t m = s.hi - s.lo;
+      HIP_TRY(copy_in(d, d.hashes, hashes + 32 * s.lo, 32 * m, 64));
+      HIP_TRY(copy_in(d, d.key_idx, skey_idx + s.lo, 4 * m, 64));
+      return sign_and_copy_out(d, d.hashes.as<uint8_t>(), d.key_idx.as<uint32_t>(), s.lo, m, out_rs, out_ok, out_der,
+                               out_der_len);
+    });
   });
 }
 
@@ -3226,29 +3139,28 @@ int pbftv_qc_verify(pbftv_ctx* ctx, const uint8_t* hashes, const uint8_t* sig_rs
 // ---------------------------------------------------------------- sha256
 int pbftv_sha256_order_dev(pbftv_ctx* ctx, int dev, const uint32_t* d_lengths, uint64_t n, uint32_t* d_order,
                            void* stream) {
-  if (!ctx || dev < 0 || dev >= (int)ctx->devs.size()) return fail(PBFTV_EINVAL, "bad context or device index");
-  Device& d = *ctx->devs[dev];
-  std::lock_guard<std::mutex> lk(d.mu);
-  HIP_TRY(hipSetDevice(d.id));
+  DevEntry e;
+  if (const int rc = e.args(ctx, dev)) return rc;
+  if (const int rc = e.enter(stream)) return rc;
+  Device& d = *e.dev;
   HIP_TRY(d.order_scratch.ensure(pbftv::sha256_order_scratch_bytes(n)));
-  hipStream_t st = pick_stream(d, stream);
-  HIP_TRY(scratch_acquire(d, st));
-  HIP_TRY(pbftv::launch_sha256_order(d_lengths, n, d_order, d.order_scratch.p, st));
-  HIP_TRY(scratch_release(d, st));
+  ScratchLease lease(d.scratch, e.st);
+  HIP_TRY(lease.acquire());
+  HIP_TRY(pbftv::launch_sha256_order(d_lengths, n, d_order, d.order_scratch.p, e.st));
+  HIP_TRY(lease.release());
   return PBFTV_OK;
 }
 
 int pbftv_sha256_batch_dev(pbftv_ctx* ctx, int dev, const uint8_t* d_data, const uint64_t* d_offsets,
                            const uint32_t* d_lengths, const uint32_t* d_order, uint64_t n, uint8_t* d_digests,
                            const uint8_t* d_expected, uint8_t* d_bitmap, void* stream) {
-  if (!ctx || dev < 0 || dev >= (int)ctx->devs.size()) return fail(PBFTV_EINVAL, "bad context or device index");
+  DevEntry e;
+  if (const int rc = e.args(ctx, dev)) return rc;
   if (n && (!d_data || !d_offsets || !d_lengths || !d_digests)) return fail(PBFTV_EINVAL, "null buffer");
   if (d_expected && !d_bitmap) return fail(PBFTV_EINVAL, "expected given without bitmap");
-  Device& d = *ctx->devs[dev];
-  std::lock_guard<std::mutex> lk(d.mu);
-  HIP_TRY(hipSetDevice(d.id));
-  hipStream_t st = pick_stream(d, stream);
-  HIP_TRY(timed(d, PBFTV_K_SHA256, st, [&] {
+  if (const int rc = e.enter(stream)) return rc;
+  hipStream_t st = e.st;
+  HIP_TRY(timed(*e.dev, PBFTV_K_SHA256, st, [&] {
     return pbftv::launch_sha256(d_data, d_offsets, d_lengths, d_order, n, d_digests, d_expected, d_bitmap, st);
   }));
   return PBFTV_OK;
@@ -3315,39 +3227,36 @@ static int sha_host(pbftv_ctx* ctx, const uint8_t* data, const uint64_t* offsets
     std::vector<uint64_t> off(m);
     for (uint64_t i = 0; i < m; ++i) off[i] = offsets[s.lo + i] - lo_b;
     const uint64_t span = hi_b - lo_b;
-    std::lock_guard<std::mutex> lk(d.mu);
-    HIP_TRY(hipSetDevice(d.id));
-    HIP_TRY(d.data.ensure(span + 64));
-    HIP_TRY(d.offsets.ensure(m * 8));
-    HIP_TRY(d.lengths.ensure(m * 4));
-    HIP_TRY(d.order.ensure(m * 4));
-    HIP_TRY(d.digests.ensure(m * 32));
-    HIP_TRY(d.order_scratch.ensure(pbftv::sha256_order_scratch_bytes(m)));
-    if (span) HIP_TRY(hipMemcpyAsync(d.data.p, data + lo_b, span, hipMemcpyHostToDevice, d.stream));
-    HIP_TRY(hipMemcpyAsync(d.offsets.p, off.data(), m * 8, hipMemcpyHostToDevice, d.stream));
-    HIP_TRY(hipMemcpyAsync(d.lengths.p, lengths + s.lo, m * 4, hipMemcpyHostToDevice, d.stream));
-    HIP_TRY(scratch_acquire(d, d.stream));
-    HIP_TRY(pbftv::launch_sha256_order(d.lengths.as<uint32_t>(), m, d.order.as<uint32_t>(), d.order_scratch.p,
-                                       d.stream));
-    HIP_TRY(scratch_release(d, d.stream));
-    uint8_t* dexp = nullptr;
-    if (expected) {
-      HIP_TRY(d.expected.ensure(m * 32));
-      HIP_TRY(d.shabits.ensure((m + 31) / 32 * 4));
-      HIP_TRY(hipMemcpyAsync(d.expected.p, expected + 32 * s.lo, m * 32, hipMemcpyHostToDevice, d.stream));
-      dexp = d.expected.as<uint8_t>();
-    }
-    HIP_TRY(timed(d, PBFTV_K_SHA256, d.stream, [&] {
-      return pbftv::launch_sha256(d.data.as<uint8_t>(), d.offsets.as<uint64_t>(), d.lengths.as<uint32_t>(),
-                                  d.order.as<uint32_t>(), m, d.digests.as<uint8_t>(), dexp, d.shabits.as<uint8_t>(),
-                                  d.stream);
-    }));
-    if (out_digests)
-      HIP_TRY(hipMemcpyAsync(out_digests + 32 * s.lo, d.digests.p, m * 32, hipMemcpyDeviceToHost, d.stream));
-    if (expected)
-      HIP_TRY(hipMemcpyAsync(out_bitmap + s.lo / 8, d.shabits.p, (m + 7) / 8, hipMemcpyDeviceToHost, d.stream));
-    HIP_TRY(hipStreamSynchronize(d.stream));
-    return PBFTV_OK;
+    return shard_round_trip(d, [&]() -> int {  // (off: read by an asynchronous copy until d.stream is synchronised)
+      HIP_TRY(d.data.ensure(span + 64));
+      HIP_TRY(d.order.ensure(m * 4));
+      HIP_TRY(d.digests.ensure(m * 32));
+      HIP_TRY(d.order_scratch.ensure(pbftv::sha256_order_scratch_bytes(m)));
+      if (span) HIP_TRY(hipMemcpyAsync(d.data.p, data + lo_b, span, hipMemcpyHostToDevice, d.stream));
+      HIP_TRY(copy_in(d, d.offsets, off.data(), m * 8, 0));
+      HIP_TRY(copy_in(d, d.lengths, lengths + s.lo, m * 4, 0));
+      ScratchLease lease(d.scratch, d.stream);
+      HIP_TRY(lease.acquire());
+      HIP_TRY(pbftv::launch_sha256_order(d.lengths.as<uint32_t>(), m, d.order.as<uint32_t>(), d.order_scratch.p,
+                                         d.stream));
+      HIP_TRY(lease.release());
+      uint8_t* dexp = nullptr;
+      if (expected) {
+        HIP_TRY(d.shabits.ensure((m + 31) / 32 * 4));
+        HIP_TRY(copy_in(d, d.expected, expected + 32 * s.lo, m * 32, 0));
+        dexp = d.expected.as<uint8_t>();
+      }
+      HIP_TRY(timed(d, PBFTV_K_SHA256, d.stream, [&] {
+        return pbftv::launch_sha256(d.data.as<uint8_t>(), d.offsets.as<uint64_t>(), d.lengths.as<uint32_t>(),
+                                    d.order.as<uint32_t>(), m, d.digests.as<uint8_t>(), dexp, d.shabits.as<uint8_t>(),
+                                    d.stream);
+      }));
+      if (out_digests)
+        HIP_TRY(hipMemcpyAsync(out_digests + 32 * s.lo, d.digests.p, m * 32, hipMemcpyDeviceToHost, d.stream));
+      if (expected)
+        HIP_TRY(hipMemcpyAsync(out_bitmap + s.lo / 8, d.shabits.p, (m + 7) / 8, hipMemcpyDeviceToHost, d.stream));
+      return PBFTV_OK;
+    });
   });
 }
 
@@ -3720,43 +3629,23 @@ static int sign_replies_by(pbftv_ctx* ctx, uint64_t n, const int64_t* view_ids, 
     const auto nid = p.add_str(node_ids, node_id_off, node_id_len, s.lo, s.hi);
     const auto res = p.add_str(results, result_off, result_len, s.lo, s.hi);
     const size_t o_key = p.add(skey_idx + s.lo, 4 * m);
-    std::lock_guard<std::mutex> lk(d.mu);
-    HIP_TRY(hipSetDevice(d.id));
-    int rc = upload(d, p);
-    if (rc != PBFTV_OK) return rc;
-    const pbftv::ReplyCols c{at<int64_t>(d, o_view), at<int64_t>(d, o_ts), str_col(d, cid), str_col(d, nid),
-                             str_col(d, res)};
-    const uint64_t* slot = at<uint64_t>(d, o_slot);
-    rc = [&]() -> int {
-      int r = encode_and_hash(d, m, slot, pre, [&] {
+    return shard_round_trip(d, [&]() -> int {
+      int rc = upload(d, p);
+      if (rc != PBFTV_OK) return rc;
+      const pbftv::ReplyCols c{at<int64_t>(d, o_view), at<int64_t>(d, o_ts), str_col(d, cid), str_col(d, nid),
+                               str_col(d, res)};
+      const uint64_t* slot = at<uint64_t>(d, o_slot);
+      rc = encode_and_hash(d, m, slot, pre, [&] {
         return pbftv::launch_gojson_reply(c, m, slot, d.data.as<uint8_t>(), d.lengths.as<uint32_t>(), d.stream);
       });
-      if (r != PBFTV_OK) return r;
-      if (out_sig_rs) {
-        HIP_TRY(d.sigs.ensure(64 * m + 64));
-        HIP_TRY(d.bitmap.ensure((m + 7) / 8 + 8));
-        r = sign_on_device(d, d.digests.as<uint8_t>(), at<uint32_t>(d, o_key), m, d.sigs.as<uint8_t>(),
-                           d.bitmap.as<uint8_t>(), d.stream);
-        if (r != PBFTV_OK) return r;
-        HIP_TRY(hipMemcpyAsync(out_sig_rs + 64 * s.lo, d.sigs.p, 64 * m, hipMemcpyDeviceToHost, d.stream));
-        if (out_ok_bitmap)
-          HIP_TRY(hipMemcpyAsync(out_ok_bitmap + s.lo / 8, d.bitmap.p, (m + 7) / 8, hipMemcpyDeviceToHost, d.stream));
-      } else {
-        HIP_TRY(d.sign.der.ensure(72 * m + 64));
-        HIP_TRY(d.sign.der_len.ensure(4 * m + 64));
-        r = sign_der_on_device(d, d.digests.as<uint8_t>(), at<uint32_t>(d, o_key), m, d.sign.der.as<uint8_t>(),
-                               d.sign.der_len.as<uint32_t>(), d.stream);
-        if (r != PBFTV_OK) return r;
-        HIP_TRY(hipMemcpyAsync(out_der + 72 * s.lo, d.sign.der.p, 72 * m, hipMemcpyDeviceToHost, d.stream));
-        HIP_TRY(hipMemcpyAsync(out_der_len + s.lo, d.sign.der_len.p, 4 * m, hipMemcpyDeviceToHost, d.stream));
-      }
+      if (rc != PBFTV_OK) return rc;
+      rc = sign_and_copy_out(d, d.digests.as<uint8_t>(), at<uint32_t>(d, o_key), s.lo, m, out_sig_rs, out_ok_bitmap,
+                             out_der, out_der_len);
+      if (rc != PBFTV_OK) return rc;
       if (out_digests)
         HIP_TRY(hipMemcpyAsync(out_digests + 32 * s.lo, d.digests.p, 32 * m, hipMemcpyDeviceToHost, d.stream));
-      HIP_TRY(hipStreamSynchronize(d.stream));
       return PBFTV_OK;
-    }();
-    if (rc != PBFTV_OK) (void)hipStreamSynchronize(d.stream);  // (the arena's staging is reused by the next call)
-    return rc;
+    });
   });
 }
 

@@ -14,7 +14,12 @@ logic tests/cpp/test_pending_frees.cpp checks on the host.  Here, on the GPU:
      create no event after the fifth cycle;
   d. pbftv_close with frees pending and work queued;
   e. pinned blocks: the reuse cache, its "at most twice the size" rule, the
-     1 GiB cap, a host-buffer verify from reused blocks.
+     1 GiB cap, a host-buffer verify from reused blocks;
+  f. one batch of every user of the device's shared scratch, alternating over
+     the context's stream, a library stream and a caller's own with no host
+     synchronisation in between and kernel timing on: every output exact, the
+     launch counts of timing ids 0..7 as enqueued, then pbftv_close with event
+     pairs nobody collected (host/scratch_order.h, host/kernel_timers.h).
 
 Inputs as in test_gpu_stream_queues.py: 32,768 distinct signatures over 10
 keys, 1 % corrupted, tiled to batches of 262,144; the reference is the
@@ -287,6 +292,139 @@ def test_close_with_pending_frees_and_queued_work(pool, ecdsa_fixtures, monkeypa
     with Verifier(device_mask=1) as v:
         v.register_keys(keys)
         assert (v.verify_batch(hashes, sigs, kidx) == expect).all()
+
+
+def test_every_scratch_user_across_three_streams_with_timing_on(oracle_lib, monkeypatch):
+    """f.  One batch of every user of the device's shared scratch -- registered
+    and carried-key (SEC1 compressed) verifies, both with DER signatures too, a
+    sign and a sign-DER batch, a SHA-256 length order -- enqueued with no host
+    synchronisation in between, alternating over the context's stream, a
+    library stream and a stream the caller made; 65 items each (a wave plus
+    one: a ragged last bitmap byte), one signature per verify corrupted, every
+    batch on the lane path, kernel timing on.  After one synchronisation every
+    output equals the oracle's or the RFC 6979 model's, and the launch counts
+    of ids 0..7, read through the three getters, are what the sequence
+    implies.  Then more DER and sign launches, and the context closes with
+    their times uncollected."""
+    import hashlib
+
+    import msgpath_cases as mc
+    import sign_cases as sc
+    import wirekey_cases as wk
+    from simple_pbft_amd import Verifier
+    from simple_pbft_amd.pbftv import KEY_SEC1_COMPRESSED
+    monkeypatch.setenv("PBFTV_GBITS", "24")  # small tables: this test is about ordering and bookkeeping
+    monkeypatch.setenv("PBFTV_QBITS", "16")
+    monkeypatch.setenv("PBFTV_WAVE_MAX", "0")
+    n, nkeys, nb = 65, 5, 9
+    ds = sc.keypool(nkeys)
+    pub = sc.pubkeys(ds)
+    hashes, kidx, model_rs = sc.batch(n, nkeys)
+
+    def corrupted(at):  # the model's signatures with one s byte flipped
+        s = model_rs.copy()
+        s[at, 40] ^= 0x10
+        return s
+
+    def oracle_bits(sigs):
+        want = np.zeros(nb, np.uint8)
+        oracle_lib.oracle_ecdsa_p256_verify_batch(hashes.ctypes.data, sigs.ctypes.data, kidx.ctypes.data, n,
+                                                  pub.ctypes.data, nkeys, want.ctypes.data, 4)
+        bits = np.unpackbits(want, bitorder="little")[:n].astype(bool)
+        assert bits.sum() == n - 1  # exactly the corrupted one fails
+        return bits
+
+    def der_column(sigs):
+        encs = [sc.der_expected(sigs[i]) for i in range(n)]
+        length = np.array([len(e) for e in encs], np.uint32)
+        off = (np.cumsum(length) - length).astype(np.uint64)
+        return np.frombuffer(b"".join(encs), np.uint8), off, length
+
+    sig_a, sig_b, sig_c, sig_d = corrupted(0), corrupted(63), corrupted(64), corrupted(17)
+    want_bits = [oracle_bits(s) for s in (sig_a, sig_b, sig_c, sig_d)]
+    carried = wk.encode(pub[kidx], KEY_SEC1_COMPRESSED)
+    want_der = [sc.der_expected(model_rs[i]) for i in range(n)]
+    msgs = [bytes([i]) * (3 + 7 * i) for i in range(n)]  # 3 .. 451 bytes: one to eight compressions
+    m_data, m_off, m_len = Verifier.pack(msgs)
+    want_digests = np.frombuffer(b"".join(hashlib.sha256(m).digest() for m in msgs), np.uint8).reshape(n, 32)
+
+    v = Verifier(device_mask=1)
+    hip, foreign = _foreign_stream()
+    try:
+        v.set_latency_path_max(0)
+        assert v.register_keys(pub).all() and v.register_signing_keys(sc.col(ds)).all()
+        lib = v.stream_create(0)
+        up = lambda a: v.to_device(0, a, pad=64)
+        dh, dk, dkeys = up(hashes), up(kidx), up(carried)
+        d_sig_a, d_sig_b = up(sig_a), up(sig_b)
+        d_der_c, d_der_d = [up(x) for x in der_column(sig_c)], [up(x) for x in der_column(sig_d)]
+        d_bits = [v.alloc(0, 64) for _ in range(4)]
+        d_rs, d_ok = v.alloc(0, 64 * n + 64), v.alloc(0, 64)
+        d_slots, d_slen = v.alloc(0, 72 * n + 64), v.alloc(0, 4 * n + 64)
+        d_msg, d_moff, d_mlen = up(m_data), up(m_off), up(m_len)
+        d_order, d_dig = v.alloc(0, 4 * n + 64), v.alloc(0, 32 * n + 64)
+        outs = d_bits + [d_rs, d_ok, d_slots, d_slen, d_order, d_dig]
+
+        def sequence():
+            v.verify_batch_dev(0, dh.ptr, d_sig_a.ptr, dk.ptr, n, d_bits[0].ptr, stream=None)
+            v.verify_wirekey_batch_dev(0, dh.ptr, d_sig_b.ptr, dkeys.ptr, KEY_SEC1_COMPRESSED, n, d_bits[1].ptr,
+                                       stream=lib)
+            v.verify_der_batch_dev(0, dh.ptr, d_der_c[0].ptr, d_der_c[1].ptr, d_der_c[2].ptr, dk.ptr, n,
+                                   d_bits[2].ptr, stream=foreign)
+            v.verify_wirekey_der_batch_dev(0, dh.ptr, d_der_d[0].ptr, d_der_d[1].ptr, d_der_d[2].ptr, dkeys.ptr,
+                                           KEY_SEC1_COMPRESSED, n, d_bits[3].ptr, stream=None)
+            v.sign_batch_dev(0, dh.ptr, dk.ptr, n, d_rs.ptr, d_ok.ptr, stream=lib)
+            v.sign_der_batch_dev(0, dh.ptr, dk.ptr, n, d_slots.ptr, d_slen.ptr, stream=foreign)
+            v.sha256_order_dev(0, d_mlen.ptr, n, d_order.ptr, stream=None)
+            v.sha256_batch_dev(0, d_msg.ptr, d_moff.ptr, d_mlen.ptr, d_order.ptr, n, d_dig.ptr, stream=None)
+
+        def wait_all():
+            v.sync(0)
+            v.stream_wait(0, lib)
+            v.stream_wait(0, foreign)
+
+        # once untimed: tables and scratch are placed (their first use synchronises inside the library)
+        sequence()
+        wait_all()
+        for b in outs:
+            b.zero()
+        v.set_kernel_timing(True)
+        v.reset_kernel_times()
+        sequence()
+        wait_all()
+
+        for j in range(4):
+            got = np.unpackbits(d_bits[j].to_host(nb), bitorder="little")[:n].astype(bool)
+            assert (got == want_bits[j]).all(), (j, np.nonzero(got != want_bits[j])[0])
+        assert (d_rs.to_host(64 * n).reshape(n, 64) == model_rs).all()
+        ok = np.unpackbits(d_ok.to_host(nb), bitorder="little")
+        assert ok[:n].all() and not ok[n:].any()
+        slots, slen = d_slots.to_host(72 * n).reshape(n, 72), d_slen.to_host(4 * n, dtype=np.uint32)
+        for i in range(n):
+            assert slen[i] == len(want_der[i]) and slots[i, :slen[i]].tobytes() == want_der[i], i
+            assert not slots[i, slen[i]:].any(), i
+        order = d_order.to_host(4 * n, dtype=np.uint32).astype(np.int64)
+        assert (np.sort(order) == np.arange(n)).all()
+        assert (np.diff(mc.sha_blocks(m_len)[order]) <= 0).all()  # most compressions first
+        assert (d_dig.to_host(32 * n).reshape(n, 32) == want_digests).all()
+
+        # ids 0..5, the DER id and the sign id, each through its own getter
+        counts = [v.kernel_time_ms(0, k)[1] for k in range(6)]
+        assert counts == [4, 2, 1, 0, 0, 2], counts  # scalars, comb, sha256, wave, gojson, varbase
+        assert v.der_kernel_time_ms(0)[1] == 2
+        assert [v.sign_kernel_time_ms(0, s)[1] for s in range(5)] == [7, 2, 2, 2, 1]
+        assert all(v.kernel_time_ms(0, k)[0] > 0 for k in (0, 1, 2, 5))
+        assert v.der_kernel_time_ms(0)[0] > 0 and v.sign_kernel_time_ms(0, 0)[0] > 0
+
+        # DER and sign launches whose times nobody collects
+        v.verify_der_batch_dev(0, dh.ptr, d_der_c[0].ptr, d_der_c[1].ptr, d_der_c[2].ptr, dk.ptr, n, d_bits[2].ptr,
+                               stream=lib)
+        v.sign_der_batch_dev(0, dh.ptr, dk.ptr, n, d_slots.ptr, d_slen.ptr, stream=foreign)
+        wait_all()
+    finally:
+        v.close()  # (returns nothing: a failure inside it would abort or hang here)
+        hip.hipStreamDestroy(ctypes_void(foreign))
+    assert v.handle is None
 
 
 def test_pinned_blocks(pool, monkeypatch):
