@@ -102,8 +102,8 @@ func replyColumns(reps []ReplyMsg) (views, ts []int64, cid, id, rs column) {
 
 // SignReplies digests and signs a batch of replies in one round trip: the
 // replica's side of FlushReplies (json.Marshal, SHA-256 and ecdsa.Sign of
-// every reply, the digests never leaving the GPU in between).  Votes need no
-// call of their own: their digests and SignBatch compose.
+// every reply, the digests never leaving the GPU in between).  SealReplies /
+// SealVotes (seal.go) return the signed wire JSON instead of bare signatures.
 func (x *Ctx) SignReplies(reps []ReplyMsg, keyIdx []uint32) (digests [][32]byte, sigs [][64]byte, ok []bool, err error) {
 	n := len(reps)
 	if len(keyIdx) != n {

@@ -49,6 +49,7 @@ extern "C" {
 #define PBFTV_ENOMEM (-4)   /* device or pinned host allocation failed */
 #define PBFTV_ENOKEYS (-5)  /* verify called before pbftv_register_keys */
 #define PBFTV_ENOSIGNKEYS (-6) /* sign called before pbftv_register_signing_keys */
+#define PBFTV_ENOSPACE (-7) /* pbftv_seal_*: out_wire is too small; *out_wire_bytes holds the size needed */
 
 typedef struct pbftv_ctx pbftv_ctx;
 
@@ -727,9 +728,8 @@ int pbftv_flush_replies_wirekey_der(pbftv_ctx* ctx, uint64_t n, const int64_t* v
  *
  * pbftv_sign_replies takes the reply columns of pbftv_digest_reply_batch and
  * does Go-JSON, SHA-256 and the signature in one round trip per device, the
- * digests staying in device memory in between; out_digests may be NULL.  Votes
- * have no call of their own: two per sequence compose from
- * pbftv_digest_vote_batch followed by pbftv_ecdsa_p256_sign_batch. */
+ * digests staying in device memory in between; out_digests may be NULL.
+ * pbftv_seal_* below return the signed messages themselves. */
 int pbftv_register_signing_keys(pbftv_ctx* ctx, const uint8_t* priv, uint32_t k, uint8_t* out_valid);
 int pbftv_ecdsa_p256_sign_batch(pbftv_ctx* ctx, const uint8_t* hashes, const uint32_t* skey_idx, uint64_t n,
                                 uint8_t* out_sig_rs, uint8_t* out_ok_bitmap);
@@ -749,6 +749,83 @@ int pbftv_sign_replies_der(pbftv_ctx* ctx, uint64_t n, const int64_t* view_ids, 
                            const uint8_t* node_ids, const uint64_t* node_id_off, const uint32_t* node_id_len,
                            const uint8_t* results, const uint64_t* result_off, const uint32_t* result_len,
                            const uint32_t* skey_idx, uint8_t* out_digests, uint8_t* out_der, uint32_t* out_der_len);
+
+/* ---- Sealing: what a replica posts, in one round trip per device ----
+ * pbftv_seal_votes / _replies / _preprepares take the columns of the matching
+ * pbftv_digest_*_batch (same string-column conventions: any order, shared
+ * bytes, the offset of an empty string is not read).  Message i is encoded to
+ * its unsigned Go-JSON preimage, hashed, signed under signing key skey_idx[i]
+ * (pbftv_register_signing_keys' set) and written in its signed wire form:
+ * exactly pbftv_gojson_vote_signed / _reply_signed / _preprepare_signed of the
+ * same fields with that signature, non-nil.  sig_format selects the signature
+ * field's bytes: PBFTV_SIG_RS, the 64 bytes r||s, or PBFTV_SIG_DER, the DER
+ * bytes crypto/ecdsa.SignASN1 writes; any other value is PBFTV_EINVAL.
+ *
+ * Pre-prepares: the embedded request carries the client's signature
+ * req_sigs[req_sig_off[i] .. + req_sig_len[i]) on the wire -- free bytes of
+ * any length, a string column like the others.  req_sig_nil[i] != 0, or a NULL
+ * req_sigs or req_sig_nil column (then for every message), means Go's nil
+ * slice, written null; a non-nil signature of length 0 is written "".  The
+ * primary's preimage embeds the unsigned request, as pbftv_gojson_preprepare
+ * does.  With has_request[i] = 0 the request is null and the signature
+ * columns' entry i is not read.
+ *
+ * out_wire receives the wire forms back to back in message order, with no
+ * padding, terminator or separator; out_wire_len[i] is message i's length,
+ * out_wire_off[i] the exclusive prefix sum of the lengths over the whole batch
+ * (across devices too) and *out_wire_bytes their total.  A row whose skey_idx
+ * is out of range or names an invalid key (or that the signer's 2^-32-rare
+ * candidate exhaustion hits) is unsigned, never an error: its
+ * length is 0, its ok bit 0, it writes no byte and its offset is the running
+ * sum.  out_digests (n*32, the signed digests) and out_ok_bitmap (LSB-first,
+ * ceil(n/8) bytes, padding bits zero) may be NULL.  A wire form is below 2^32
+ * bytes.
+ *
+ * n = 0 returns PBFTV_OK and writes only *out_wire_bytes = 0; n >= 2^32, a
+ * NULL column, skey_idx, out_wire_off, out_wire_len or out_wire_bytes (or a
+ * NULL out_wire with wire_cap > 0) is PBFTV_EINVAL; without signing keys the
+ * calls return PBFTV_ENOSIGNKEYS.  If the total exceeds wire_cap the call
+ * returns PBFTV_ENOSPACE: *out_wire_bytes holds the size needed, out_wire_off,
+ * out_wire_len, out_digests and out_ok_bitmap are filled, and nothing is
+ * written to out_wire; the same call with a buffer of that size gives the
+ * full result.  No trial call is needed: with T = 103 (PBFTV_SIG_RS) or 111
+ * (PBFTV_SIG_DER), the signature tail  ,"signature":"<base64>"  of 64 or 72
+ * bytes, message i takes at most
+ *   vote         120 + 6 (digest_len + node_id_len) + T
+ *   reply        102 + 6 (client_id_len + node_id_len + result_len) + T
+ *   pre-prepare  189 + 6 (digest_len + req_client_id_len + req_operation_len)
+ *                + T + 15 + 4 ceil(req_sig_len / 3)
+ * bytes (the Go-JSON bound of its strings, 6 bytes per input byte, plus the
+ * tails), and the sum over the batch is enough for wire_cap.
+ *
+ * Host forms only.  With several devices the shards' bytes pass through host
+ * memory once more to land behind each other; with one device the blob is
+ * copied straight from the device into out_wire. */
+#define PBFTV_SIG_RS  0  /* r||s, 64 B                          */
+#define PBFTV_SIG_DER 1  /* ASN.1 DER, 8..72 B                  */
+int pbftv_seal_votes(pbftv_ctx* ctx, uint64_t n, const int64_t* view_ids, const int64_t* sequence_ids,
+                     const uint8_t* digests, const uint64_t* digest_off, const uint32_t* digest_len,
+                     const uint8_t* node_ids, const uint64_t* node_id_off, const uint32_t* node_id_len,
+                     const int64_t* msg_types, const uint32_t* skey_idx, int sig_format, uint8_t* out_wire,
+                     uint64_t wire_cap, uint64_t* out_wire_off, uint32_t* out_wire_len, uint64_t* out_wire_bytes,
+                     uint8_t* out_digests, uint8_t* out_ok_bitmap);
+int pbftv_seal_replies(pbftv_ctx* ctx, uint64_t n, const int64_t* view_ids, const int64_t* timestamps,
+                       const uint8_t* client_ids, const uint64_t* client_id_off, const uint32_t* client_id_len,
+                       const uint8_t* node_ids, const uint64_t* node_id_off, const uint32_t* node_id_len,
+                       const uint8_t* results, const uint64_t* result_off, const uint32_t* result_len,
+                       const uint32_t* skey_idx, int sig_format, uint8_t* out_wire, uint64_t wire_cap,
+                       uint64_t* out_wire_off, uint32_t* out_wire_len, uint64_t* out_wire_bytes, uint8_t* out_digests,
+                       uint8_t* out_ok_bitmap);
+int pbftv_seal_preprepares(pbftv_ctx* ctx, uint64_t n, const int64_t* view_ids, const int64_t* sequence_ids,
+                           const uint8_t* digests, const uint64_t* digest_off, const uint32_t* digest_len,
+                           const uint8_t* has_request, const int64_t* req_timestamps, const uint8_t* req_client_ids,
+                           const uint64_t* req_client_id_off, const uint32_t* req_client_id_len,
+                           const uint8_t* req_operations, const uint64_t* req_operation_off,
+                           const uint32_t* req_operation_len, const int64_t* req_sequence_ids,
+                           const uint8_t* req_sigs, const uint64_t* req_sig_off, const uint32_t* req_sig_len,
+                           const uint8_t* req_sig_nil, const uint32_t* skey_idx, int sig_format, uint8_t* out_wire,
+                           uint64_t wire_cap, uint64_t* out_wire_off, uint32_t* out_wire_len,
+                           uint64_t* out_wire_bytes, uint8_t* out_digests, uint8_t* out_ok_bitmap);
 
 /* Quorum certificate: verify n signatures and count acceptances.
  * *out_accepted = popcount; *out_quorum = (*out_accepted >= quorum).  With

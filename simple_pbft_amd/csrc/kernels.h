@@ -283,4 +283,44 @@ hipError_t launch_preprepare_verify(const int64_t* view, const int64_t* seq, con
                                    const uint8_t* req_digests, const StateCols& s, uint64_t n, uint8_t* msg_ok,
                                    hipStream_t st);
 
+// ---- Sealed wire forms (seal_kernels.hip, wire.h) ----
+// The signatures of a batch as the signer left them: signature i is the len[i]
+// bytes (len == nullptr: 64) at sig + stride * i -- r||s rows (stride 64) or
+// the DER writer's slots (stride 72) and lengths -- and counts only where
+// okbits (LSB-first, not null) has a 1.
+struct SealSigs {
+  const uint8_t* sig;
+  uint32_t stride;
+  const uint32_t* len;
+  const uint8_t* okbits;
+};
+// the clients' signatures inside pre-prepares: a string column and one nil
+// byte per message (read only where has_req)
+struct SealReqSigs {
+  StrCol col;
+  const uint8_t* nil;
+};
+// out_len[i] = the signed wire length of message i from the encoder's preimage
+// length pre_len[i] (wire.h), 0 where its ok bit is 0.  has_req == nullptr:
+// votes and replies (rq is not read); else pre-prepares.
+hipError_t launch_seal_lengths(const uint32_t* pre_len, const SealSigs& s, const uint8_t* has_req,
+                               const SealReqSigs& rq, uint64_t n, uint32_t* out_len, hipStream_t st);
+// off[i] = len[0] + .. + len[i-1] in 64 bits, *total = their sum: three
+// launches in stream order (no workgroup waits on another); scratch:
+// seal_scan_scratch_bytes(n).  n < 2^32.
+size_t seal_scan_scratch_bytes(uint64_t n);
+hipError_t launch_seal_offsets(const uint32_t* len, uint64_t n, void* scratch, uint64_t* off, uint64_t* total,
+                               hipStream_t st);
+// message i's *_signed encoding (gojson_enc.h) to blob + off[i], exactly
+// len[i] bytes (none where len[i] == 0); dump: kSealDumpBytes that take what a
+// wrong length would have put past a message's end (never read)
+constexpr uint32_t kSealDumpBytes = 32;
+hipError_t launch_seal_votes(const VoteCols& c, const SealSigs& s, uint64_t n, const uint64_t* off,
+                             const uint32_t* len, uint8_t* blob, uint8_t* dump, hipStream_t st);
+hipError_t launch_seal_replies(const ReplyCols& c, const SealSigs& s, uint64_t n, const uint64_t* off,
+                               const uint32_t* len, uint8_t* blob, uint8_t* dump, hipStream_t st);
+hipError_t launch_seal_preprepares(const PrePrepareCols& c, const SealSigs& s, const SealReqSigs& rq, uint64_t n,
+                                   const uint64_t* off, const uint32_t* len, uint8_t* blob, uint8_t* dump,
+                                   hipStream_t st);
+
 }  // namespace pbftv

@@ -376,6 +376,12 @@ struct Device {
     bool have = false;
     DevBuf rec, rs, okb, der, der_len;
   } sign;
+  // Sealing (seal_kernels.hip): the wire lengths and offsets of a shard, the
+  // scan's block sums, its total and the blob of wire bytes (one of each per
+  // device; used on d.stream alone, under d.mu, behind the signer's lease).
+  struct Seal {
+    DevBuf len, off, scan, total, blob;
+  } seal;
 };
 
 // key-order scratch: a fresh allocation gets its header zeroed (the sort's
@@ -1285,6 +1291,7 @@ const char* pbftv_strerror(int code) {
     case PBFTV_ENOMEM: return "out of memory";
     case PBFTV_ENOKEYS: return "no keys registered";
     case PBFTV_ENOSIGNKEYS: return "no signing keys registered";
+    case PBFTV_ENOSPACE: return "output buffer too small";
     default: return "unknown error";
   }
 }
@@ -1341,7 +1348,8 @@ void pbftv_close(pbftv_ctx* ctx) {
     (void)collect_times(*d);
     d->timers.drop();  // (what could not be read: no event pair outlives the context)
     (void)sign_wipe_keys(*d);  // zeros over the private keys before their memory goes back
-    for (DevBuf* b : {&d->sign.keys, &d->sign.rec, &d->sign.rs, &d->sign.okb, &d->sign.der, &d->sign.der_len})
+    for (DevBuf* b : {&d->sign.keys, &d->sign.rec, &d->sign.rs, &d->sign.okb, &d->sign.der, &d->sign.der_len,
+                      &d->seal.len, &d->seal.off, &d->seal.scan, &d->seal.total, &d->seal.blob})
       b->release();
     for (auto& b : d->qblocks) b->release();
     for (auto& b : d->tab_scratch) b.release();
@@ -3902,6 +3910,301 @@ int pbftv_flush_votes_der(pbftv_ctx* ctx, uint64_t n, const int64_t* view_ids, c
   return flush_votes_sig(ctx, n, view_ids, sequence_ids, digests, digest_off, digest_len, node_ids, node_id_off,
                          node_id_len, msg_types, der_sigs(der, der_off, der_len), key_idx, n_states, state_view_ids,
                          state_last_seqs, state_req_digests, state_idx, out_digests, out_sig_bitmap, out_msg_bitmap);
+}
+
+// ---- sealing: the signed wire form of what a replica sends (seal_kernels.hip, wire.h) ----
+extern "C++" {
+namespace {
+
+struct SealOut {
+  uint8_t* wire;
+  uint64_t cap;
+  uint64_t* off;
+  uint32_t* len;
+  uint64_t* bytes;
+  uint8_t* digests;
+  uint8_t* ok;
+};
+
+// One message kind's shard on its device: where its columns lie in the arena,
+// its encoder, its writer.
+struct VoteSeal {
+  size_t o_slot, o_view, o_seq, o_type;
+  Packer::Str dg, nid;
+  uint64_t pre;
+  pbftv::VoteCols cols(const Device& d) const {
+    return {at<int64_t>(d, o_view), at<int64_t>(d, o_seq), str_col(d, dg), str_col(d, nid), at<int64_t>(d, o_type)};
+  }
+  const uint8_t* has_req(const Device&) const { return nullptr; }
+  pbftv::SealReqSigs req_sigs(const Device&) const { return {{nullptr, nullptr, nullptr}, nullptr}; }
+  int encode(Device& d, uint64_t m) const {
+    const pbftv::VoteCols c = cols(d);
+    const uint64_t* slot = at<uint64_t>(d, o_slot);
+    return encode_and_hash(d, m, slot, pre, [&] {
+      return pbftv::launch_gojson_vote(c, m, slot, d.data.as<uint8_t>(), d.lengths.as<uint32_t>(),
+                                       pbftv::StateCols{nullptr, nullptr, nullptr, nullptr, 0}, nullptr, d.stream);
+    });
+  }
+  hipError_t write(Device& d, const pbftv::SealSigs& sg, uint64_t m, uint8_t* blob, uint8_t* dump) const {
+    return pbftv::launch_seal_votes(cols(d), sg, m, d.seal.off.as<uint64_t>(), d.seal.len.as<uint32_t>(), blob, dump,
+                                    d.stream);
+  }
+};
+
+struct ReplySeal {
+  size_t o_slot, o_view, o_ts;
+  Packer::Str cid, nid, res;
+  uint64_t pre;
+  pbftv::ReplyCols cols(const Device& d) const {
+    return {at<int64_t>(d, o_view), at<int64_t>(d, o_ts), str_col(d, cid), str_col(d, nid), str_col(d, res)};
+  }
+  const uint8_t* has_req(const Device&) const { return nullptr; }
+  pbftv::SealReqSigs req_sigs(const Device&) const { return {{nullptr, nullptr, nullptr}, nullptr}; }
+  int encode(Device& d, uint64_t m) const {
+    const pbftv::ReplyCols c = cols(d);
+    const uint64_t* slot = at<uint64_t>(d, o_slot);
+    return encode_and_hash(d, m, slot, pre, [&] {
+      return pbftv::launch_gojson_reply(c, m, slot, d.data.as<uint8_t>(), d.lengths.as<uint32_t>(), d.stream);
+    });
+  }
+  hipError_t write(Device& d, const pbftv::SealSigs& sg, uint64_t m, uint8_t* blob, uint8_t* dump) const {
+    return pbftv::launch_seal_replies(cols(d), sg, m, d.seal.off.as<uint64_t>(), d.seal.len.as<uint32_t>(), blob,
+                                      dump, d.stream);
+  }
+};
+
+struct PrePrepareSeal {
+  size_t o_slot, o_view, o_seq, o_has, o_rts, o_rseq, o_rnil;
+  Packer::Str dg, cid, op, rsig;
+  uint64_t pre;
+  pbftv::PrePrepareCols cols(const Device& d) const {
+    return {at<int64_t>(d, o_view), at<int64_t>(d, o_seq), str_col(d, dg), at<uint8_t>(d, o_has),
+            {at<int64_t>(d, o_rts), str_col(d, cid), str_col(d, op), at<int64_t>(d, o_rseq)}};
+  }
+  const uint8_t* has_req(const Device& d) const { return at<uint8_t>(d, o_has); }
+  pbftv::SealReqSigs req_sigs(const Device& d) const { return {str_col(d, rsig), at<uint8_t>(d, o_rnil)}; }
+  int encode(Device& d, uint64_t m) const {
+    const pbftv::PrePrepareCols c = cols(d);
+    const uint64_t* slot = at<uint64_t>(d, o_slot);
+    return encode_and_hash(d, m, slot, pre, [&] {
+      return pbftv::launch_gojson_preprepare(c, m, slot, d.data.as<uint8_t>(), d.lengths.as<uint32_t>(), d.stream);
+    });
+  }
+  hipError_t write(Device& d, const pbftv::SealSigs& sg, uint64_t m, uint8_t* blob, uint8_t* dump) const {
+    return pbftv::launch_seal_preprepares(cols(d), sg, req_sigs(d), m, d.seal.off.as<uint64_t>(),
+                                          d.seal.len.as<uint32_t>(), blob, dump, d.stream);
+  }
+};
+
+// The checks every seal call makes after its own columns' null checks; > 0: done (n == 0)
+int seal_args(pbftv_ctx* ctx, uint64_t n, bool columns_ok, const uint32_t* skey_idx, int sig_format,
+              const SealOut& out) {
+  if (!ctx) return fail(PBFTV_EINVAL, "ctx is null");
+  if (!out.bytes) return fail(PBFTV_EINVAL, "out_wire_bytes is null");
+  if (sig_format != PBFTV_SIG_RS && sig_format != PBFTV_SIG_DER) return fail(PBFTV_EINVAL, "unknown signature format");
+  if (n >> 32) return fail(PBFTV_EINVAL, "n must be below 2^32");
+  if (n == 0) {
+    *out.bytes = 0;
+    return 1;
+  }
+  if (!columns_ok || !skey_idx || !out.off || !out.len || (out.cap && !out.wire))
+    return fail(PBFTV_EINVAL, "null buffer");
+  if (!sign_keys_ready(ctx)) return fail(PBFTV_ENOSIGNKEYS, "pbftv_register_signing_keys has not been called");
+  return PBFTV_OK;
+}
+
+// Encode, hash, sign, measure, scan and write each shard in one round trip on
+// its device (prep(p, shard) packs the kind's columns and returns its *Seal).
+// One shard: the total comes back first, then the blob goes straight into the
+// caller's buffer.  Several: a shard cannot know the totals before it, so its
+// blob waits in host memory until all are in, and its offsets are rebased.
+template <class Prep>
+int seal_by(pbftv_ctx* ctx, uint64_t n, const uint32_t* skey_idx, int sig_format, const SealOut& out, Prep prep) {
+  const auto shards = plan_shards(n, ctx->devs.size());
+  const bool single = shards.size() <= 1;
+  std::vector<uint64_t> totals(shards.size(), 0);
+  std::vector<std::vector<uint8_t>> staged(single ? 0 : shards.size());
+  const bool der = sig_format == PBFTV_SIG_DER;
+  const int rc = run_sharded(ctx, n, [&](Device& d, Shard s) -> int {
+    const uint64_t m = s.hi - s.lo;
+    size_t idx = 0;
+    while (shards[idx].lo != s.lo) ++idx;
+    Packer p;
+    const auto k = prep(p, s);
+    const size_t o_key = p.add(skey_idx + s.lo, 4 * m);
+    return shard_round_trip(d, [&]() -> int {
+      int r = upload(d, p);
+      if (r != PBFTV_OK) return r;
+      r = k.encode(d, m);
+      if (r != PBFTV_OK) return r;
+      // The signer takes the scratch lease for its buffers; what follows reads
+      // them and uses d.seal on the same stream, d.mu held until it is
+      // synchronised: the own stream's fence, recorded when another stream
+      // next asks for the scratch, lies behind all of it (as for
+      // sign_and_copy_out's copies).
+      pbftv::SealSigs sg;
+      if (der) {
+        HIP_TRY(d.sign.der.ensure(72 * m + 64));
+        HIP_TRY(d.sign.der_len.ensure(4 * m + 64));
+        r = sign_der_on_device(d, d.digests.as<uint8_t>(), at<uint32_t>(d, o_key), m, d.sign.der.as<uint8_t>(),
+                               d.sign.der_len.as<uint32_t>(), d.stream);
+        sg = {d.sign.der.as<uint8_t>(), 72, d.sign.der_len.as<uint32_t>(), d.sign.okb.as<uint8_t>()};
+      } else {
+        HIP_TRY(d.sigs.ensure(64 * m + 64));
+        HIP_TRY(d.bitmap.ensure((m + 7) / 8 + 8));
+        r = sign_on_device(d, d.digests.as<uint8_t>(), at<uint32_t>(d, o_key), m, d.sigs.as<uint8_t>(),
+                           d.bitmap.as<uint8_t>(), d.stream);
+        sg = {d.sigs.as<uint8_t>(), 64, nullptr, d.bitmap.as<uint8_t>()};
+      }
+      if (r != PBFTV_OK) return r;
+      HIP_TRY(d.seal.len.ensure(4 * m + 64));
+      HIP_TRY(d.seal.off.ensure(8 * m + 64));
+      HIP_TRY(d.seal.scan.ensure(pbftv::seal_scan_scratch_bytes(m) + 64));
+      HIP_TRY(d.seal.total.ensure(64));
+      HIP_TRY(d.mout.ensure(64));
+      HIP_TRY(pbftv::launch_seal_lengths(d.lengths.as<uint32_t>(), sg, k.has_req(d), k.req_sigs(d), m,
+                                         d.seal.len.as<uint32_t>(), d.stream));
+      HIP_TRY(pbftv::launch_seal_offsets(d.seal.len.as<uint32_t>(), m, d.seal.scan.p, d.seal.off.as<uint64_t>(),
+                                         d.seal.total.as<uint64_t>(), d.stream));
+      HIP_TRY(hipMemcpyAsync(d.mout.p, d.seal.total.p, 8, hipMemcpyDeviceToHost, d.stream));
+      HIP_TRY(hipMemcpyAsync(out.len + s.lo, d.seal.len.p, 4 * m, hipMemcpyDeviceToHost, d.stream));
+      HIP_TRY(hipMemcpyAsync(out.off + s.lo, d.seal.off.p, 8 * m, hipMemcpyDeviceToHost, d.stream));
+      if (out.digests)
+        HIP_TRY(hipMemcpyAsync(out.digests + 32 * s.lo, d.digests.p, 32 * m, hipMemcpyDeviceToHost, d.stream));
+      if (out.ok)  // (a shard starts at a multiple of kShardAlign: on a byte of the bitmap)
+        HIP_TRY(hipMemcpyAsync(out.ok + s.lo / 8, sg.okbits, (m + 7) / 8, hipMemcpyDeviceToHost, d.stream));
+      HIP_TRY(hipStreamSynchronize(d.stream));
+      const uint64_t total = *d.mout.as<uint64_t>();
+      totals[idx] = total;
+      if (total == 0 || total > out.cap) return PBFTV_OK;  // (nothing to write, or PBFTV_ENOSPACE below)
+      HIP_TRY(d.seal.blob.ensure(total + pbftv::kSealDumpBytes + 64));
+      uint8_t* blob = d.seal.blob.as<uint8_t>();
+      HIP_TRY(k.write(d, sg, m, blob, blob + total));
+      uint8_t* dst = out.wire;
+      if (!single) {
+        staged[idx].resize(total);
+        dst = staged[idx].data();
+      }
+      HIP_TRY(hipMemcpyAsync(dst, blob, total, hipMemcpyDeviceToHost, d.stream));
+      return PBFTV_OK;
+    });
+  });
+  if (rc != PBFTV_OK) return rc;
+  uint64_t sum = 0;
+  for (size_t i = 0; i < shards.size(); ++i) {
+    if (sum)
+      for (uint64_t j = shards[i].lo; j < shards[i].hi; ++j) out.off[j] += sum;
+    sum += totals[i];
+  }
+  *out.bytes = sum;
+  if (sum > out.cap) return fail(PBFTV_ENOSPACE, "out_wire is smaller than the sealed batch (see *out_wire_bytes)");
+  if (!single) {
+    uint64_t base = 0;
+    for (size_t i = 0; i < shards.size(); ++i) {
+      if (totals[i]) std::memcpy(out.wire + base, staged[i].data(), totals[i]);
+      base += totals[i];
+    }
+  }
+  return PBFTV_OK;
+}
+
+}  // namespace
+}  // extern "C++"
+
+int pbftv_seal_votes(pbftv_ctx* ctx, uint64_t n, const int64_t* view_ids, const int64_t* sequence_ids,
+                     const uint8_t* digests, const uint64_t* digest_off, const uint32_t* digest_len,
+                     const uint8_t* node_ids, const uint64_t* node_id_off, const uint32_t* node_id_len,
+                     const int64_t* msg_types, const uint32_t* skey_idx, int sig_format, uint8_t* out_wire,
+                     uint64_t wire_cap, uint64_t* out_wire_off, uint32_t* out_wire_len, uint64_t* out_wire_bytes,
+                     uint8_t* out_digests, uint8_t* out_ok_bitmap) {
+  const SealOut out{out_wire, wire_cap, out_wire_off, out_wire_len, out_wire_bytes, out_digests, out_ok_bitmap};
+  const bool cols = view_ids && sequence_ids && digest_off && digest_len && node_id_off && node_id_len && msg_types;
+  if (const int rc = seal_args(ctx, n, cols, skey_idx, sig_format, out)) return rc > 0 ? PBFTV_OK : rc;
+  return seal_by(ctx, n, skey_idx, sig_format, out, [&](Packer& p, Shard s) {
+    const uint64_t m = s.hi - s.lo;
+    VoteSeal k;
+    k.o_slot = p.add_owned(slots(s.lo, s.hi, [&](uint64_t i) {
+      return pbftv::gojson::vote_bound(digest_len[i], node_id_len[i]);
+    }, &k.pre));
+    k.o_view = p.add(view_ids + s.lo, 8 * m);
+    k.o_seq = p.add(sequence_ids + s.lo, 8 * m);
+    k.o_type = p.add(msg_types + s.lo, 8 * m);
+    k.dg = p.add_str(digests, digest_off, digest_len, s.lo, s.hi);
+    k.nid = p.add_str(node_ids, node_id_off, node_id_len, s.lo, s.hi);
+    return k;
+  });
+}
+
+int pbftv_seal_replies(pbftv_ctx* ctx, uint64_t n, const int64_t* view_ids, const int64_t* timestamps,
+                       const uint8_t* client_ids, const uint64_t* client_id_off, const uint32_t* client_id_len,
+                       const uint8_t* node_ids, const uint64_t* node_id_off, const uint32_t* node_id_len,
+                       const uint8_t* results, const uint64_t* result_off, const uint32_t* result_len,
+                       const uint32_t* skey_idx, int sig_format, uint8_t* out_wire, uint64_t wire_cap,
+                       uint64_t* out_wire_off, uint32_t* out_wire_len, uint64_t* out_wire_bytes, uint8_t* out_digests,
+                       uint8_t* out_ok_bitmap) {
+  const SealOut out{out_wire, wire_cap, out_wire_off, out_wire_len, out_wire_bytes, out_digests, out_ok_bitmap};
+  const bool cols = view_ids && timestamps && client_id_off && client_id_len && node_id_off && node_id_len &&
+                    result_off && result_len;
+  if (const int rc = seal_args(ctx, n, cols, skey_idx, sig_format, out)) return rc > 0 ? PBFTV_OK : rc;
+  return seal_by(ctx, n, skey_idx, sig_format, out, [&](Packer& p, Shard s) {
+    const uint64_t m = s.hi - s.lo;
+    ReplySeal k;
+    k.o_slot = p.add_owned(slots(s.lo, s.hi, [&](uint64_t i) {
+      return pbftv::gojson::reply_bound(client_id_len[i], node_id_len[i], result_len[i]);
+    }, &k.pre));
+    k.o_view = p.add(view_ids + s.lo, 8 * m);
+    k.o_ts = p.add(timestamps + s.lo, 8 * m);
+    k.cid = p.add_str(client_ids, client_id_off, client_id_len, s.lo, s.hi);
+    k.nid = p.add_str(node_ids, node_id_off, node_id_len, s.lo, s.hi);
+    k.res = p.add_str(results, result_off, result_len, s.lo, s.hi);
+    return k;
+  });
+}
+
+int pbftv_seal_preprepares(pbftv_ctx* ctx, uint64_t n, const int64_t* view_ids, const int64_t* sequence_ids,
+                           const uint8_t* digests, const uint64_t* digest_off, const uint32_t* digest_len,
+                           const uint8_t* has_request, const int64_t* req_timestamps, const uint8_t* req_client_ids,
+                           const uint64_t* req_client_id_off, const uint32_t* req_client_id_len,
+                           const uint8_t* req_operations, const uint64_t* req_operation_off,
+                           const uint32_t* req_operation_len, const int64_t* req_sequence_ids,
+                           const uint8_t* req_sigs, const uint64_t* req_sig_off, const uint32_t* req_sig_len,
+                           const uint8_t* req_sig_nil, const uint32_t* skey_idx, int sig_format, uint8_t* out_wire,
+                           uint64_t wire_cap, uint64_t* out_wire_off, uint32_t* out_wire_len,
+                           uint64_t* out_wire_bytes, uint8_t* out_digests, uint8_t* out_ok_bitmap) {
+  const SealOut out{out_wire, wire_cap, out_wire_off, out_wire_len, out_wire_bytes, out_digests, out_ok_bitmap};
+  // a NULL req_sigs or req_sig_nil column: every client signature is Go's nil slice
+  const bool all_nil = !req_sigs || !req_sig_nil;
+  const bool cols = view_ids && sequence_ids && digest_off && digest_len && has_request && req_timestamps &&
+                    req_client_id_off && req_client_id_len && req_operation_off && req_operation_len &&
+                    req_sequence_ids && (all_nil || (req_sig_off && req_sig_len));
+  if (const int rc = seal_args(ctx, n, cols, skey_idx, sig_format, out)) return rc > 0 ? PBFTV_OK : rc;
+  // the client signatures as the device takes them: nil (and length 0, so its
+  // offset is not read) where there is no request or the slice is nil
+  std::vector<uint8_t> rnil(n);
+  std::vector<uint32_t> rlen(n);
+  for (uint64_t i = 0; i < n; ++i) {
+    rnil[i] = all_nil || !has_request[i] || req_sig_nil[i] ? 1 : 0;
+    rlen[i] = rnil[i] ? 0 : req_sig_len[i];
+  }
+  return seal_by(ctx, n, skey_idx, sig_format, out, [&](Packer& p, Shard s) {
+    const uint64_t m = s.hi - s.lo;
+    PrePrepareSeal k;
+    k.o_slot = p.add_owned(slots(s.lo, s.hi, [&](uint64_t i) {
+      return pbftv::gojson::preprepare_bound(digest_len[i], has_request[i] ? req_client_id_len[i] : 0,
+                                             has_request[i] ? req_operation_len[i] : 0);
+    }, &k.pre));
+    k.o_view = p.add(view_ids + s.lo, 8 * m);
+    k.o_seq = p.add(sequence_ids + s.lo, 8 * m);
+    k.o_has = p.add(has_request + s.lo, m);
+    k.o_rts = p.add(req_timestamps + s.lo, 8 * m);
+    k.o_rseq = p.add(req_sequence_ids + s.lo, 8 * m);
+    k.o_rnil = p.add(rnil.data() + s.lo, m);
+    k.dg = p.add_str(digests, digest_off, digest_len, s.lo, s.hi);
+    k.cid = p.add_str(req_client_ids, req_client_id_off, req_client_id_len, s.lo, s.hi);
+    k.op = p.add_str(req_operations, req_operation_off, req_operation_len, s.lo, s.hi);
+    k.rsig = p.add_str(req_sigs, req_sig_off, rlen.data(), s.lo, s.hi);
+    return k;
+  });
 }
 
 int pbftv_verify_msg_batch(int64_t state_view_id, int64_t state_last_seq, const uint8_t req_digest[32], uint64_t n,

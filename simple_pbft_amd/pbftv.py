@@ -24,11 +24,16 @@ PBFTV_EDEVICE = -3
 PBFTV_ENOMEM = -4
 PBFTV_ENOKEYS = -5
 PBFTV_ENOSIGNKEYS = -6
+PBFTV_ENOSPACE = -7
 
 # key formats of the *_wirekey entry points (include/pbftv.h PBFTV_KEY_*)
 KEY_XY = 0                 # X||Y, 64 B
 KEY_SEC1_COMPRESSED = 1    # 02|03 || X, 33 B
 KEY_SEC1_UNCOMPRESSED = 2  # 04 || X || Y, 65 B
+
+# signature formats of the seal calls (include/pbftv.h PBFTV_SIG_*)
+SIG_RS = 0   # r||s, 64 B
+SIG_DER = 1  # ASN.1 DER, 8..72 B
 
 _u8p = ctypes.POINTER(ctypes.c_uint8)
 _u32p = ctypes.POINTER(ctypes.c_uint32)
@@ -184,6 +189,12 @@ def lib() -> ctypes.CDLL:
                                                                _vp]),
         "pbftv_sign_replies": (ctypes.c_int, [_vp, ctypes.c_uint64] + [_vp] * 15),
         "pbftv_sign_replies_der": (ctypes.c_int, [_vp, ctypes.c_uint64] + [_vp] * 15),
+        "pbftv_seal_votes": (ctypes.c_int, [_vp, ctypes.c_uint64] + [_vp] * 10 + [ctypes.c_int, _vp, ctypes.c_uint64] +
+                             [_vp] * 5),
+        "pbftv_seal_replies": (ctypes.c_int, [_vp, ctypes.c_uint64] + [_vp] * 12 +
+                               [ctypes.c_int, _vp, ctypes.c_uint64] + [_vp] * 5),
+        "pbftv_seal_preprepares": (ctypes.c_int, [_vp, ctypes.c_uint64] + [_vp] * 19 +
+                                   [ctypes.c_int, _vp, ctypes.c_uint64] + [_vp] * 5),
         "pbftv_qc_verify": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_uint64, ctypes.c_uint32, _vp,
                                            ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_int)]),
     }
@@ -452,6 +463,29 @@ class PrePrepareColumns:
         return [self.view.ctypes.data, self.seq.ctypes.data, db.ctypes.data, do.ctypes.data, dl.ctypes.data,
                 self.has.ctypes.data, self.rts.ctypes.data, cb.ctypes.data, co.ctypes.data, cl.ctypes.data,
                 ob.ctypes.data, oo.ctypes.data, ol.ctypes.data, self.rseq.ctypes.data]
+
+
+class Sealed:
+    """What a seal call returns: the wire forms back to back in `blob`, message
+    i's bytes at blob[off[i] : off[i] + len[i]] (none where ok[i] is False),
+    the signed digests (or None) and the ok flags.  Unpacks as
+    (blob, off, len, digests, ok); sealed[i] / iteration yield the bytes."""
+
+    def __init__(self, blob, off, length, digests, ok):
+        self.blob, self.off, self.len, self.digests, self.ok = blob, off, length, digests, ok
+
+    def __iter__(self):
+        return iter((self.blob, self.off, self.len, self.digests, self.ok))
+
+    def __len__(self):
+        return len(self.len)
+
+    def __getitem__(self, i: int) -> bytes:
+        o = int(self.off[i])
+        return self.blob[o:o + int(self.len[i])].tobytes()
+
+    def messages(self):
+        return [self[i] for i in range(len(self))]
 
 
 def _sig_inputs(n: int, sigs, key_idx, what: str):
@@ -1007,6 +1041,56 @@ class Verifier:
         _check(self._L.pbftv_sign_replies_der(self._h, n, *cols.args(), skey_idx.ctypes.data, _ptr(out_d),
                                               der.ctypes.data, ln.ctypes.data))
         return (out_d[:n] if out_d is not None else None, der[:n], ln[:n])
+
+    # ---- sealing: Go-JSON, SHA-256, signature and the signed wire form in one round trip
+    def _seal(self, fn, n: int, args, skey_idx, sig_format: int, digests: bool, wire_cap: int | None) -> "Sealed":
+        skey_idx = np.ascontiguousarray(skey_idx, np.uint32)
+        assert skey_idx.shape[0] == n
+        off, ln = np.zeros(max(n, 1), np.uint64), np.zeros(max(n, 1), np.uint32)
+        out_d = np.zeros((max(n, 1), 32), np.uint8) if digests else None
+        bm = np.zeros((n + 7) // 8 + 1, np.uint8)
+        total = ctypes.c_uint64(0)
+
+        def call(blob):
+            return fn(self._h, n, *args, skey_idx.ctypes.data, sig_format, _ptr(blob) if len(blob) else None,
+                      len(blob), off.ctypes.data, ln.ctypes.data, ctypes.byref(total), _ptr(out_d), bm.ctypes.data)
+
+        blob = np.zeros(wire_cap or 0, np.uint8)
+        rc = call(blob)
+        if rc == PBFTV_ENOSPACE and wire_cap is None:  # sized by a trial call
+            blob = np.zeros(total.value, np.uint8)
+            rc = call(blob)
+        _check(rc)
+        return Sealed(blob[:total.value], off[:n], ln[:n], out_d[:n] if out_d is not None else None,
+                      bitmap_to_bool(bm, n))
+
+    def seal_votes(self, cols: "VoteColumns", skey_idx, sig_format: int = SIG_RS, digests: bool = True,
+                   wire_cap: int | None = None) -> "Sealed":
+        """pbftv_seal_votes: (blob, off, len, digests | None, ok).  wire_cap None: the buffer
+        is sized by a first call that returns PBFTV_ENOSPACE; else a too-small cap raises it."""
+        return self._seal(self._L.pbftv_seal_votes, cols.n, cols.args(), skey_idx, sig_format, digests, wire_cap)
+
+    def seal_replies(self, cols: "ReplyColumns", skey_idx, sig_format: int = SIG_RS, digests: bool = True,
+                     wire_cap: int | None = None) -> "Sealed":
+        """pbftv_seal_replies: (blob, off, len, digests | None, ok)."""
+        return self._seal(self._L.pbftv_seal_replies, cols.n, cols.args(), skey_idx, sig_format, digests, wire_cap)
+
+    def seal_preprepares(self, cols: "PrePrepareColumns", req_sigs, skey_idx, sig_format: int = SIG_RS,
+                         digests: bool = True, wire_cap: int | None = None) -> "Sealed":
+        """pbftv_seal_preprepares: req_sigs is None (every client signature nil) or one entry per
+        message, bytes or None (nil); (blob, off, len, digests | None, ok)."""
+        if req_sigs is None:
+            extra = [None, None, None, None]
+        else:
+            assert len(req_sigs) == cols.n
+            rb, ro, rl = self.pack([s or b"" for s in req_sigs])
+            nil = np.array([s is None for s in req_sigs], np.uint8)
+            if len(rb) == 0:
+                rb = np.zeros(1, np.uint8)
+            extra = [rb.ctypes.data, ro.ctypes.data, rl.ctypes.data, nil.ctypes.data]
+            keep = (rb, ro, rl, nil)  # noqa: F841  (alive across the call)
+        return self._seal(self._L.pbftv_seal_preprepares, cols.n, cols.args() + extra, skey_idx, sig_format, digests,
+                          wire_cap)
 
     def table_config(self):
         """(G window bits, key window bits, table bytes per device)."""
