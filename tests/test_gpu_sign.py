@@ -327,3 +327,176 @@ def test_timing_id_7_counts_launches_and_resets(ver):
         ver.set_kernel_timing(False)
     ver.sign_batch(hashes, kidx)
     assert ver.sign_kernel_time_ms(0, 0) == (0.0, 0)  # timing off: nothing recorded
+
+
+# ---------------------------------------------------------------- seam hashes through the public calls
+def test_seam_hashes_and_end_keys_through_the_public_calls():
+    """H1_SEAM x D_ENDS -- the hash at 0, 1, n - 1, n, n + 1 and 2^256 - 1 under
+    the keys 1, 2, n - 2 and n - 1 -- among ordinary rows, through sign_batch,
+    sign_der_batch and their _dev forms: the model's bytes, and the library's
+    own verify accepts them under the matching public keys."""
+    import sign_stage_cases as ssc
+    ds = list(sc.D_ENDS) + list(sc.keypool(NKEYS))
+    seam = sc.drbg_cases()[:len(sc.H1_SEAM) * len(sc.D_ENDS)]
+    bh, bk, bw = sc.batch(65 - len(seam), NKEYS)
+    hashes = np.concatenate([sc.col([h for _, h in seam]), bh])
+    kidx = np.concatenate([np.array([sc.D_ENDS.index(d) for d, _ in seam], np.uint32), bk + len(sc.D_ENDS)])
+    want = np.concatenate([ssc.chain_expected()[:len(seam)], bw])
+    n = len(kidx)
+    encs = [sc.der_expected(want[i]) for i in range(n)]
+    with Verifier(device_mask=1) as v:
+        assert v.register_signing_keys(sc.col(ds)).all()
+        assert v.register_keys(sc.pubkeys(ds)).all()
+        sig, bm = raw_bitmap(v, hashes, kidx)
+        assert (sig == want).all(), np.nonzero((sig != want).any(axis=1))[0]
+        nb = (n + 7) // 8
+        bits = np.unpackbits(bm[:nb], bitorder="little")
+        assert bits[:n].all() and not bits[n:].any() and (bm[nb:] == 0xFF).all()
+        assert v.verify_batch(hashes, sig, kidx).all()
+        der, ln = v.sign_der_batch(hashes, kidx)
+        for i in range(n):
+            assert ln[i] == len(encs[i]) and der[i, :ln[i]].tobytes() == encs[i] and not der[i, ln[i]:].any(), i
+        col = DerColumn(blob=der.reshape(-1), off=(72 * np.arange(n)).astype(np.uint64), length=ln.astype(np.uint32))
+        assert v.verify_der_batch(hashes, col, kidx).all()
+        dh, dk = v.to_device(0, hashes), v.to_device(0, kidx)
+        dsig = v.to_device(0, np.full(64 * n + 64, 0xEE, np.uint8))
+        dok = v.to_device(0, np.full(nb + 8, 0xFF, np.uint8))
+        dd = v.to_device(0, np.full(72 * n + 64, 0xEE, np.uint8))
+        dl = v.to_device(0, np.full(n + 4, 0xEEEEEEEE, np.uint32))
+        try:
+            v.sign_batch_dev(0, dh.ptr, dk.ptr, n, dsig.ptr, dok.ptr)
+            v.sign_der_batch_dev(0, dh.ptr, dk.ptr, n, dd.ptr, dl.ptr)
+            v.sync(0)
+            gs, go, gd, gl = dsig.to_host(), dok.to_host(), dd.to_host(), dl.to_host(dtype=np.uint32)
+        finally:
+            for b in (dh, dk, dsig, dok, dd, dl):
+                b.free()
+        assert (gs[:64 * n].reshape(n, 64) == want).all() and (gs[64 * n:] == 0xEE).all()
+        assert (go[:nb] == bm[:nb]).all() and (go[nb:] == 0xFF).all()
+        assert (gd[:72 * n].reshape(n, 72) == der).all() and (gd[72 * n:] == 0xEE).all()
+        assert (gl[:n] == ln).all() and (gl[n:] == 0xEEEEEEEE).all()
+
+
+# ---------------------------------------------------------------- two logical devices
+@pytest.fixture
+def two_devices(monkeypatch):
+    monkeypatch.setenv("PBFTV_ALIAS_DEVICES", "2")
+    v = Verifier()
+    assert v.device_count() == 2 and v.device_id(0) == v.device_id(1)
+    assert v.register_signing_keys(sc.col(sc.keypool(NKEYS))).all()
+    yield v
+    v.close()
+
+
+SHARD_ALIGN = 512  # pbftv_api.cpp kShardAlign: a host form's shards begin at multiples of it
+
+
+def _seam(n, ndev=2):
+    per = -(-n // ndev)
+    return -(-per // SHARD_ALIGN) * SHARD_ALIGN
+
+
+def raw_sign_calls(v, hashes, cols, kidx, rkidx):
+    """Every host form of the signer with its outputs poisoned first and slack past
+    each: name -> the arrays as written."""
+    L, c, n = v._L, v._h, len(kidx)
+    nb = (n + 7) // 8
+    hp, kp, rp = hashes.ctypes.data, kidx.ctypes.data, rkidx.ctypes.data
+    out = {}
+
+    def bufs():
+        return (np.full((n + 1, 64), 0xEE, np.uint8), np.full(nb + 8, 0xFF, np.uint8),
+                np.full((n + 1, 72), 0xEE, np.uint8), np.full(n + 4, 0xEEEEEEEE, np.uint32),
+                np.full((n + 1, 32), 0xA5, np.uint8))
+
+    sig, bm, der, ln, dg = bufs()
+    assert L.pbftv_ecdsa_p256_sign_batch(c, hp, kp, n, sig.ctypes.data, bm.ctypes.data) == PBFTV_OK
+    out["sign_batch"] = (sig, bm)
+    sig, bm, der, ln, dg = bufs()
+    assert L.pbftv_ecdsa_p256_sign_batch(c, hp, kp, n, sig.ctypes.data, None) == PBFTV_OK
+    out["sign_batch, no bitmap"] = (sig,)
+    assert L.pbftv_ecdsa_p256_sign_der_batch(c, hp, kp, n, der.ctypes.data, ln.ctypes.data) == PBFTV_OK
+    out["sign_der_batch"] = (der, ln)
+    sig, bm, der, ln, dg = bufs()
+    assert L.pbftv_sign_replies(c, n, *cols.args(), rp, dg.ctypes.data, sig.ctypes.data, bm.ctypes.data) == PBFTV_OK
+    out["sign_replies"] = (dg, sig, bm)
+    sig, bm, der, ln, dg = bufs()
+    assert L.pbftv_sign_replies(c, n, *cols.args(), rp, None, sig.ctypes.data, bm.ctypes.data) == PBFTV_OK
+    out["sign_replies, no digests"] = (sig, bm)
+    assert L.pbftv_sign_replies_der(c, n, *cols.args(), rp, dg.ctypes.data, der.ctypes.data,
+                                    ln.ctypes.data) == PBFTV_OK
+    out["sign_replies_der"] = (dg, der, ln)
+    return out
+
+
+@pytest.mark.parametrize("n", [513, 1031, 2049])
+def test_two_devices_give_one_devices_signatures(ver, two_devices, n):
+    """The sign host forms sharded over two logical devices: every output equal to
+    the one-device call's byte for byte, the first 96 rows equal to the model,
+    unsigned rows at the ends and on both sides of the shard seam, exact bits
+    there, untouched poison past every output -- and a smaller key set reaches
+    both shards."""
+    seam = _seam(n)
+    assert 0 < seam < n
+    bad = sorted({0, 511, 512, n - 1, seam - 1, seam} | ({seam + 9} if seam + 9 < n else set()))
+    hashes, kidx, want = sc.batch(n, NKEYS)
+    kidx, want = kidx.copy(), want.copy()
+    cols = ReplyColumns(mc.layout_batch("reply", n))
+    rkidx = (np.arange(n) * 3 % NKEYS).astype(np.uint32)
+    for j, i in enumerate(bad):
+        kidx[i] = rkidx[i] = (NKEYS, BIG, 1 << 31)[j % 3]
+        want[i] = 0
+    ok = np.ones(n, bool)
+    ok[bad] = False
+    nb = (n + 7) // 8
+    want_bm = np.packbits(ok, bitorder="little")  # padding bits zero
+    cfg = two_devices.table_config()
+    one = raw_sign_calls(ver, hashes, cols, kidx, rkidx)
+    two = raw_sign_calls(two_devices, hashes, cols, kidx, rkidx)
+    assert one.keys() == two.keys()
+    for name in one:
+        for a, b in zip(one[name], two[name]):
+            assert np.array_equal(a, b), name
+    # ... and "equal" is not "equally wrong": rows, bits and poison of the two-device outputs on their own
+    sig, bm = two["sign_batch"]
+    assert (sig[:96] == want[:96]).all() and (sig[:n] == want).all() and (sig[n] == 0xEE).all()
+    assert (bm[:nb] == want_bm).all() and (bm[nb:] == 0xFF).all()
+    assert (two["sign_batch, no bitmap"][0][:n] == want).all() and (two["sign_batch, no bitmap"][0][n] == 0xEE).all()
+    der, ln = two["sign_der_batch"]
+    for i in list(range(96)) + bad:
+        enc = sc.der_expected(want[i]) if ok[i] else b""
+        assert ln[i] == len(enc) and der[i, :len(enc)].tobytes() == enc and not der[i, len(enc):].any(), i
+    assert ((ln[:n] == 0) == ~ok).all() and (der[n] == 0xEE).all() and (ln[n:] == 0xEEEEEEEE).all()
+    dg, rsig, rbm = two["sign_replies"]
+    want_d = ver.digest_reply_batch(cols)
+    assert (dg[:n] == want_d).all() and (dg[n] == 0xA5).all()
+    rwant = reply_want(want_d[:96], np.where(ok[:96], rkidx[:96], 0).astype(np.uint32)).copy()
+    rwant[~ok[:96]] = 0
+    assert (rsig[:96] == rwant).all() and not rsig[:n][~ok].any() and (rsig[n] == 0xEE).all()
+    assert (rbm[:nb] == want_bm).all() and (rbm[nb:] == 0xFF).all()
+    fd, fok = ver.flush_replies(cols, rsig[:n], np.where(ok, rkidx, 0).astype(np.uint32))
+    assert (fok == ok).all()  # every signed reply, past the first 96 too, verifies under its key
+    nsig, nbm = two["sign_replies, no digests"]
+    assert np.array_equal(nsig, rsig) and np.array_equal(nbm, rbm)
+    dg2, rder, rln = two["sign_replies_der"]
+    assert (dg2[:n] == want_d).all() and (dg2[n] == 0xA5).all()
+    for i in list(range(96)) + bad:
+        enc = sc.der_expected(rwant[i]) if ok[i] else b""  # (a row past the first 96 is here because it is unsigned)
+        assert rln[i] == len(enc) and rder[i, :len(enc)].tobytes() == enc and not rder[i, len(enc):].any(), i
+    assert ((rln[:n] == 0) == ~ok).all() and (rder[n] == 0xEE).all() and (rln[n:] == 0xEEEEEEEE).all()
+    # a smaller key set, registered on both devices: an index it no longer has is unsigned on both shards
+    try:
+        assert two_devices.register_signing_keys(sc.col(sc.keypool(NKEYS)[:2])).all()
+        sig2, ok2 = two_devices.sign_batch(hashes, kidx)
+        keep = ok & (kidx < 2)
+        for shard in (slice(0, seam), slice(seam, n)):  # (n = 513: the second shard is one unsigned row)
+            assert ok[shard].sum() < 16 or (keep[shard].any() and (~keep & ok)[shard].any())
+        assert (ok2 == keep).all() and (sig2[keep] == want[keep]).all() and not sig2[~keep].any()
+        der2, ln2 = two_devices.sign_der_batch(hashes, kidx)
+        assert ((ln2 == 0) == ~keep).all() and not der2[~keep].any()
+    finally:
+        assert two_devices.register_signing_keys(sc.col(sc.keypool(NKEYS))).all()
+    sig3, ok3 = two_devices.sign_batch(hashes, kidx)
+    assert (ok3 == ok).all() and (sig3 == want).all()
+    assert two_devices.table_config() == cfg
+
